@@ -2,7 +2,7 @@
 """Headline benchmark: 4K (3840x2160) frame pairs interpolated per second (BASELINE.json metric, config 2:
 single 4K frame pair, 5-scale test path, t = 0.5) through the MI355X-native hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one (frame pair, t) forward = the reference's `model_net(input_gpuList, t, normInput=pyramid, ...)` call
@@ -17,6 +17,11 @@ JSON line on CPU only (tests/test_distributed_cpu.py).
 
 The timed loop rotates DISTINCT frame pairs (>= 4, one per in-flight stream and more): consecutive steps never read
 the same pyramid, and the pyramids together (4 x 377 MB) exceed the 256 MiB Infinity Cache.
+
+`--dump-outputs DIR` writes what the timed loop computed in its LAST timed step on rank 0 (the interpolated frame a caller of
+fldr_harness.interpolate receives) to DIR as .npy, float64: the whole frame when it fits in DUMP_BYTES, otherwise a fixed sample of
+it drawn with DUMP_SEED (the same positions in every run of the same shape).  The inputs are seeded synthetic pairs, so two builds
+run with the same arguments can be compared output for output (a DIR named bench_out* inside the tree is ignored by git).
 """
 import argparse
 import json
@@ -35,6 +40,8 @@ PEAK_FP16_MFMA_TFLOPS = 2500.0      # dense fp16/bf16 matrix peak
 PEAK_HBM_GBPS = 8000.0
 # SURVEY.md App. C / BASELINE.md section 3: compulsory HBM traffic and algorithmic FLOPs of ONE forward
 PATH_MODEL = {(2160, 3840): {"hbm_bytes": 5.284e9, "flops": 0.314e12}, (2160, 4096): {"hbm_bytes": 5.636e9, "flops": 0.335e12}}
+DUMP_BYTES = 48 << 20               # --dump-outputs: at most this many bytes of array data (a sample of larger frames)
+DUMP_SEED = 20261015
 
 
 def parse():
@@ -63,7 +70,14 @@ def parse():
     ap.add_argument("--dry", action="store_true", help="no GPU work: a step is a 1 ms sleep (CPU test of the launcher / reductions)")
     ap.add_argument("--share-gpu", action="store_true", help="REHEARSAL on a 1-GPU box: all N ranks run their GPU work on device 0 (process group: gloo); exercises the "
                                                              "multi-process launch, per-rank sharding, barriers and reductions around real HIP work - the line says so and its value is no measurement")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the frame rank 0's last timed step computed to DIR/<name>.npy "
+                                                                         "(float64; a fixed seeded sample when the frame exceeds %d MiB)" % (DUMP_BYTES >> 20))
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.dry:
+        ap.error("--dump-outputs needs the GPU path: a --dry run computes nothing")
+    return a
 
 
 def self_launch(a):
@@ -198,6 +212,22 @@ def host_info():
     return dict(host_core_budget(), cpu_model=model)
 
 
+def dump_outputs(d, frame):
+    """--dump-outputs: `frame` (CPU tensor, the last timed step's output) as DIR/frame.npy, or, when larger than DUMP_BYTES, the values at
+    DUMP_BYTES / 8 flat positions drawn without replacement by numpy's seeded generator (sorted) as DIR/frame_sample.npy.  -> {name: shape}"""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    x = frame.double().contiguous().numpy()
+    if x.nbytes <= DUMP_BYTES:
+        arrays = {"frame": x}
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, DUMP_BYTES // 8, replace=False))
+        arrays = {"frame_sample": x.reshape(-1)[idx]}
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), v)
+    return {name: list(v.shape) for name, v in arrays.items()}
+
+
 def cpu_baseline(frames_cpu, t_cpu, gpu_out=None, runs=3):
     """The oracle (CPU restatement of the reference, kind 'port') timed on this box's host cores on the SAME 4K pair:
     1 warm-up + `runs` timed forwards with every core this process may use (3 at one GPU; 1 on rank 0 of a multi-GPU
@@ -296,7 +326,12 @@ def main():
 
     def barrier():
         if use_pg:
-            dist.barrier()
+            if gpu:
+                dist.barrier()
+            else:
+                # --dry: gloo's own barrier.  dist.barrier() asks the runtime for an accelerator first, which initialises HIP (opens
+                # the GPU) in every rank of a CPU-only launch on a GPU host
+                dist.monitored_barrier()
 
     npairs = max(a.pairs, a.streams, 1)
     my_pairs = shard_pairs(world * npairs, rank, world)          # pair index = seed; disjoint across ranks
@@ -414,6 +449,8 @@ def main():
     dt_local, out = timed_region()
     if gpu and graph_state["on"] and not verify_graphs():          # a replay that differs from its eager frame: nothing of it is reported
         dt_local, out = timed_region()
+    # --dump-outputs: the last timed step's frame, copied now (a graph replay returns its slot's buffer, which the legs below replay into)
+    dumped = out.detach().cpu() if (gpu and a.dump_outputs and rank == 0) else None
     # ---- sustained rate: the same loop for >= --sustained-s seconds (clocks settle, caches in steady state) ---
     dt = max_over_ranks(dt_local, device)
     if gpu:
@@ -463,7 +500,7 @@ def main():
         # Every collective of the run is behind us: release the other ranks NOW.  What follows on rank 0 (informational legs, roofline
         # of the dominant kernel, the CPU baseline: ~1 min) involves no other rank, so none of them waits in a barrier that a slow or
         # stuck leg would turn into a collective timeout over there.
-        dist.barrier()
+        barrier()
         dist.destroy_process_group()
     if rank != 0:
         return
@@ -709,6 +746,9 @@ def main():
             if x_test is not None:
                 res["x_test"] = dict(x_test, dir=a.xtest_dir, multiple=a.xtest_multiple)
                 res.setdefault("parity", {})["x_test_psnr"] = x_test["psnr"]
+        if dumped is not None:
+            res["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dump_outputs(a.dump_outputs, dumped), "seed": DUMP_SEED,
+                                   "what": "rank 0's frame of the last timed step (pair %d, t=0.5), float64" % my_pairs[(a.steps - 1) % npairs]}
         print(json.dumps(res), flush=True)
 
 

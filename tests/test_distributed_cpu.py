@@ -29,7 +29,7 @@ def _worker(rank, world, port, q):
     psum, cnt = sum(30.0 + i for i in mine), len(mine)
     mean, n = Hn.reduce_psnr(psum, cnt)
     tmax = Hn.max_over_ranks(0.1 * (rank + 1))
-    dist.barrier()
+    dist.monitored_barrier()          # (dist.barrier() probes the runtime for an accelerator: it would open the GPU on a GPU host)
     q.put((rank, mine, mean, n, tmax))
     dist.destroy_process_group()
 
@@ -165,7 +165,7 @@ def _eval_worker(rank, world, port, q):
     mean_s, n2 = Hn.reduce_psnr(ssum, cnt)
     tmax = Hn.max_over_ranks(0.01 * (rank + 1))
     rates = Hn.gather_floats(100.0 + rank)
-    dist.barrier()
+    dist.monitored_barrier()          # (dist.barrier() probes the runtime for an accelerator: it would open the GPU on a GPU host)
     q.put((rank, mine, mean_p, mean_s, n, n2, tmax, rates))
     dist.destroy_process_group()
 

@@ -2220,6 +2220,40 @@ def test_bench_two_ranks_share_the_gpu_rehearsal(dev, clean_launcher):
     assert j["config"]["parallelism"].startswith("dp2")
 
 
+@pytest.mark.timeout(600)
+def test_bench_dump_outputs_are_the_last_timed_frame(dev, model, clean_launcher, tmp_path):
+    """`bench.py --dump-outputs DIR` (the output-for-output comparison of two builds): two runs with the same arguments write the same
+    float64 frame bit for bit, and that frame is the forward of the pair the LAST timed step interpolated (--steps 3 over 4 pairs:
+    pair 2, t = 0.5) — computed here in-process from the same seeded synthetic pair.  540x960: the whole frame fits the dump budget."""
+    import json
+    import os
+    import sys
+    import fldr_harness as Hn
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    frames = []
+    for run in ("a", "b"):
+        d = str(tmp_path / run)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--height", "540", "--width", "960",
+               "--sustained-s", "0", "--no-cpu-baseline", "--varying-motion-steps", "0", "--incl-ingest-steps", "0", "--multi-t-pairs", "0",
+               "--fp16-mode-steps", "0", "--config5-steps", "0", "--dump-outputs", d]
+        r = clean_launcher(cmd, env=env, timeout=540)
+        assert r["rc"] == 0, (r["stdout"][-2000:], r["stderr"][-4000:])
+        js = [json.loads(l) for l in r["stdout"].splitlines() if l.startswith("{")]
+        assert len(js) == 1 and js[0]["steps"] == 3 and js[0]["ms_per_step"] > 0, r["stdout"][-2000:]
+        assert js[0]["dump_outputs"]["arrays"] == {"frame": [1, 3, 540, 960]}, js[0]["dump_outputs"]
+        assert sorted(os.listdir(d)) == ["frame.npy"]
+        f = np.load(os.path.join(d, "frame.npy"))
+        assert f.dtype == np.float64 and f.shape == (1, 3, 540, 960) and np.isfinite(f).all()
+        frames.append(f)
+    assert np.array_equal(frames[0], frames[1])
+    m, a = model
+    fr = Hn.frames_from_uint8(Hn.synthetic_pair(540, 960, seed=2)).to(dev)
+    with torch.no_grad():
+        ref = Hn.interpolate(m, a, fr, torch.tensor([[0.5]], device=dev)).cpu().numpy()
+    assert np.abs(frames[0] - ref).max() <= 1e-6, np.abs(frames[0] - ref).max()
+
+
 def test_evaluate_dir_matches_per_frame_pipeline(hip, dev, model, tmp_path):
     """fldr_harness.evaluate_dir (the dataset-shaped entry: main.py:815-911) on a folder of PNG frames written here — one scene of
     5 frames, multiple = 4: the pair (0, 4) and its three intermediate targets — against the per-frame pipeline the other tests

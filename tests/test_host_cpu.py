@@ -191,6 +191,8 @@ def test_import_contract_of_the_reference_drivers():
         m = importlib.import_module(mod)
         assert os.path.dirname(os.path.abspath(m.__file__)).startswith(os.path.join(ROOT, "fldr-vfi_amd")), (mod, m.__file__)
         for name in c["names"]:
+            if not hasattr(m, name) and importlib.util.find_spec(mod + "." + name) is not None:
+                importlib.import_module(mod + "." + name)     # `from OpticalFlow import correlation` binds a submodule, as the statement would
             assert hasattr(m, name), "%s does not define %s (imported by %s)" % (mod, name, c["importers"])
         ns = {}
         exec("from %s import *" % mod, ns)
@@ -227,43 +229,74 @@ def test_training_only_names_raise_when_called_not_at_import():
     assert float(useful.distillation_loss(fl, torch.zeros(1, 4, 32, 32), "cpu")) >= 0.0
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="the reference tree only exists in the build container")
 def test_reference_driver_imports_against_this_package():
-    """The drop-in claim of INTEGRATION.md, executed: with fldr-vfi_amd/ first on the path, the reference's
-    run_on_your_images.py (its import block and args_config) and main.py's import block run against THIS package's
-    fLDRnet / softSplat / pca_comp / useful / OpticalFlow (third-party packages this image lacks are inert placeholders)."""
+    """The drop-in claim of INTEGRATION.md, executed: with fldr-vfi_amd/ first on the path, the top-level import statements of the
+    reference's drivers main.py and run_on_your_images.py (and of utils.py, which both star-import) run against THIS package's
+    fLDRnet / softSplat / pca_comp / useful / OpticalFlow.  The statements are rebuilt from tests/golden/driver_import_blocks.json
+    (tools/make_golden.py: module / name / alias records collected with `ast`); third-party packages this image lacks and the
+    reference's own non-shadowed modules are inert placeholders."""
     import subprocess
     import sys
     code = r'''
-import sys, types, ast
+import ast, importlib, json, sys, types
 class Inert(types.ModuleType):
     def __getattr__(self, n):
         if n.startswith("__"): raise AttributeError(n)
         m = Inert(self.__name__ + "." + n); setattr(self, n, m); return m
     def __call__(self, *a, **k): return Inert("call")
-for n in ("cupy", "cv2", "skimage", "skimage.feature", "skimage.metrics", "skimage.transform", "torchvision",
-          "torchvision.transforms", "torchvision.models", "torchvision.utils", "torch.utils.tensorboard"):
-    sys.modules[n] = Inert(n)
-sys.path[:0] = [%r, "/root/reference"]
-sys.argv = ["x"]
-import run_on_your_images as R
-import fLDRnet, softSplat, pca_comp, useful
-for m in (fLDRnet, softSplat, pca_comp, useful):
+pkg, fixture = sys.argv[1], sys.argv[2]
+sys.path.insert(0, pkg)
+blocks = json.load(open(fixture))
+assert set(blocks) == {"main.py", "run_on_your_images.py", "utils.py"}, sorted(blocks)
+SHADOWED = ("fLDRnet", "softSplat", "pca_comp", "useful", "OpticalFlow")
+def node(s):
+    if "import" in s:
+        return ast.Import(names=[ast.alias(name=n, asname=a) for n, a in s["import"]])
+    return ast.ImportFrom(module=s["from"], names=[ast.alias(name=n, asname=a) for n, a in s["names"]], level=s["level"])
+def modules(s):
+    return [n for n, _ in s["import"]] if "import" in s else [s["from"]]
+def run(stmts, ns):
+    for s in stmts:
+        for m in modules(s):
+            if m == "utils" or m == "__future__":
+                continue
+            try:
+                importlib.import_module(m)
+            except ImportError:
+                assert m.split(".")[0] not in SHADOWED, m
+                parts = m.split(".")                       # a package this image lacks, or a module of the reference this package does not mirror
+                for k in range(1, len(parts) + 1):
+                    name = ".".join(parts[:k])
+                    if name not in sys.modules or (k == len(parts) and not isinstance(sys.modules[name], Inert)):
+                        sys.modules[name] = Inert(name)
+                    if k > 1:
+                        setattr(sys.modules[".".join(parts[:k - 1])], parts[k - 1], sys.modules[name])
+        mod = ast.Module(body=[node(s)], type_ignores=[])
+        exec(compile(ast.fix_missing_locations(mod), "driver_imports", "exec"), ns)
+# utils.py is the reference's own helper module: here it is what its import block binds (the names `from utils import *` passes on)
+utils = types.ModuleType("utils")
+run(blocks["utils.py"], utils.__dict__)
+sys.modules["utils"] = utils
+import fLDRnet, softSplat, pca_comp, useful, OpticalFlow
+for m in (fLDRnet, softSplat, pca_comp, useful, OpticalFlow):
     assert "fldr-vfi_amd" in m.__file__, m.__file__
-assert R.DCTXVFInet is fLDRnet.DCTXVFInet and R.to_pca is pca_comp.to_pca
-a = R.args_config()
-assert a.net_object is fLDRnet.DCTXVFInet and a.S_tst == 5 and a.dctvfi_nf == 16
-# main.py: execute only its import block (the module body parses the command line and starts a run)
-src = open("/root/reference/main.py").read()
-tree = ast.parse(src)
-imports = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom))]
-ns = {}
-exec(compile(ast.Module(imports, []), "main_imports", "exec"), ns)
-assert ns["DCTXVFInet"] is fLDRnet.DCTXVFInet and ns["ScaleIt"] is useful.ScaleIt and ns["Softsplat"] is softSplat.Softsplat
+assert utils.Softsplat is softSplat.Softsplat and utils.torch_prints is useful.torch_prints
+ns_r, ns_m = {}, {}
+run(blocks["run_on_your_images.py"], ns_r)
+run(blocks["main.py"], ns_m)
+for ns in (ns_r, ns_m):
+    assert ns["DCTXVFInet"] is fLDRnet.DCTXVFInet and ns["to_pca"] is pca_comp.to_pca and ns["DCTParams"] is pca_comp.DCTParams
+    assert ns["getmodelconfig"] is useful.getmodelconfig and ns["Softsplat"] is softSplat.Softsplat
+assert ns_m["ScaleIt"] is useful.ScaleIt and ns_m["MyPWC"] is useful.MyPWC and ns_m["distillation_loss"] is useful.distillation_loss
+# the namespace run_on_your_images.args_config() builds (tests/golden/args_papermodel_test5scales.json pins it field by field)
+import fldr_harness
+a = fldr_harness.args_config()
+assert a.net_object is ns_r["DCTXVFInet"] and a.S_tst == 5 and a.dctvfi_nf == 16
 model = a.net_object(a)
 print("OK", type(model).__module__)
-''' % os.path.join(ROOT, "fldr-vfi_amd")
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
+'''
+    r = subprocess.run([sys.executable, "-c", code, os.path.join(ROOT, "fldr-vfi_amd"), os.path.join(ROOT, "tests", "golden", "driver_import_blocks.json")],
+                       capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "OK fLDRnet" in r.stdout, r.stdout + r.stderr
 
 

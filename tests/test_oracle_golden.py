@@ -8,6 +8,17 @@ import pytest
 import torch
 
 CASES = ["model_256x256_t0500", "model_200x500_t0125"]
+# tools/make_golden.py captured the fixtures with torch.set_num_threads(8): torch-CPU's convolutions split their reductions by
+# the thread count, so the bit-for-bit comparisons below hold at that count, whatever the host's own default is
+GOLDEN_THREADS = 8
+
+
+@pytest.fixture(autouse=True)
+def _golden_thread_count():
+    prev = torch.get_num_threads()
+    torch.set_num_threads(GOLDEN_THREADS)
+    yield
+    torch.set_num_threads(prev)
 
 
 def _run(oracle, weights, g, keep):

@@ -309,6 +309,26 @@ def import_contract(out_path):
     print("wrote", out_path, {m: len(c["names"]) + len(c["star_names"]) for m, c in out.items()})
 
 
+def driver_imports(out_path):
+    """tests/golden/driver_import_blocks.json: the top-level import statements of main.py and run_on_your_images.py (the drivers)
+    and of utils.py (which both star-import), as module / name / alias records collected with `ast`, in file order.  Names only; no
+    reference code is copied.  tests/test_host_cpu.py::test_reference_driver_imports_against_this_package rebuilds and runs them."""
+    import ast
+    import json
+    out = {}
+    for f in ("main.py", "run_on_your_images.py", "utils.py"):
+        stmts = []
+        for n in ast.parse(open(os.path.join(REF, f)).read()).body:
+            if isinstance(n, ast.Import):
+                stmts.append({"import": [[a.name, a.asname] for a in n.names]})
+            elif isinstance(n, ast.ImportFrom):
+                stmts.append({"from": n.module, "level": n.level, "names": [[a.name, a.asname] for a in n.names]})
+        out[f] = stmts
+    with open(out_path, "w") as fh:
+        json.dump(out, fh, indent=1)
+    print("wrote", out_path, {f: len(s) for f, s in out.items()})
+
+
 # --test3scales / --test4scales / --test6scales / --test7scales (main.py:243-268): what main.py does to the namespace after
 # --papermodel, then one small forward of the reference at that pyramid depth (frames + output frame only).
 DEPTH_CASES = {3: (100, 150, 0.5, 21), 4: (128, 200, 0.25, 22), 6: (300, 400, 0.5, 23), 7: (520, 530, 0.75, 24)}   # reflect padding needs H, W > half the unit
@@ -359,6 +379,7 @@ def depth_cases(R, fLDRnet, pca_comp, args, gold):
 def main():
     if "--contract-only" in sys.argv:
         import_contract(os.path.join(ROOT, "tests", "golden", "import_contract.json"))
+        driver_imports(os.path.join(ROOT, "tests", "golden", "driver_import_blocks.json"))
         return
     if "--depths-only" in sys.argv:
         if sys.flags.optimize < 1:
@@ -397,6 +418,7 @@ def main():
     with open(os.path.join(gold, "args_papermodel_test5scales.json"), "w") as f:
         json.dump({n: getattr(args, n) for n in names if hasattr(args, n)}, f, indent=1, sort_keys=True)
     import_contract(os.path.join(gold, "import_contract.json"))
+    driver_imports(os.path.join(gold, "driver_import_blocks.json"))
     depth_cases(R, fLDRnet, pca_comp, args, gold)
 
 
