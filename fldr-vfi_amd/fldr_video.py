@@ -1,0 +1,233 @@
+"""ctypes binding of libfldr_video.so (video API: include/fldr_video.h) — frame interpolation on 8-bit YUV 4:2:0 frames (NV12, I420).
+
+    nv = NativeVideo(fldr_model.NativeModel.from_npz(fldr_harness.DEFAULT_WEIGHTS))
+    outs = nv.forward((f0, f1), t=[0.5], in_format=Format("nv12"), out_format=Format("nv12"))   # -> list of n_t output frames
+    s = Session(native_model, H, W, n_t=3, in_format=Format("i420"))    # host frames (numpy planes), each uploaded once
+    outs = s.push((y, u, v))                                            # [] on the first push, n_t frames afterwards
+
+A device frame is a tuple of 2-D uint8 device tensors, one per plane (NV12: Y, UV; I420: Y, U, V), each [rows, row bytes] with
+stride(1) == 1; the pitch is stride(0), so views into wider buffers work.  Host frames of a Session are the same as numpy arrays.
+Every forward enqueues on torch's current stream of the model's device and returns without synchronising.  No fallback: a missing
+library raises at load.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+import fldr_model
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libfldr_video.so")
+VIDEO_VERSION = 100               # include/fldr_video.h: FLDR_VIDEO_VERSION
+
+LAYOUTS = {"nv12": 0, "i420": 1}
+MATRICES = {"bt601": 0, "bt709": 1}
+RANGES = {"limited": 0, "full": 1}
+E_ARG, E_FORMAT, E_PITCH, E_PLANE, E_WORKSPACE, E_DEVICE = -100, -101, -102, -103, -104, -105
+
+
+class Format(ctypes.Structure):
+    _fields_ = [("layout", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
+
+    def __init__(self, layout="nv12", matrix="bt709", range="limited"):
+        super().__init__(LAYOUTS.get(layout, layout) if isinstance(layout, str) else layout,
+                         MATRICES[matrix] if isinstance(matrix, str) else matrix, RANGES[range] if isinstance(range, str) else range)
+
+    @property
+    def name(self):
+        return {0: "nv12", 1: "i420"}.get(self.layout, self.layout)
+
+
+class Frame(ctypes.Structure):
+    _fields_ = [("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
+
+
+class IO(ctypes.Structure):
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("in_", Frame * 2), ("out_format", Format),
+                ("n_t", ctypes.c_int32), ("t", ctypes.c_void_p), ("out", ctypes.POINTER(Frame))]
+
+
+class SessionConfig(ctypes.Structure):
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("out_format", Format), ("n_t", ctypes.c_int32),
+                ("device", ctypes.c_int32), ("t", ctypes.POINTER(ctypes.c_float)), ("reserved", ctypes.c_int32 * 4)]
+
+
+_SIGNATURES = {
+    "fldr_video_version": (ctypes.c_int, []),
+    "fldr_video_error_string": (ctypes.c_char_p, [ctypes.c_int]),
+    "fldr_video_sizeof": (ctypes.c_int, [ctypes.c_int]),
+    "fldr_video_workspace_bytes": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "fldr_video_forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IO), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "fldr_video_session_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SessionConfig), ctypes.POINTER(ctypes.c_void_p)]),
+    "fldr_video_session_push": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.POINTER(Frame), ctypes.POINTER(ctypes.c_int)]),
+    "fldr_video_session_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "fldr_video_session_destroy": (None, [ctypes.c_void_p]),
+}
+EXPORTS = tuple(_SIGNATURES)
+_lib = None
+
+
+class VideoError(RuntimeError):
+    def __init__(self, what, code):
+        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_video_error_string(code).decode(), code))
+        self.code = code
+
+
+def lib():
+    """The loaded libfldr_video.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
+    global _lib
+    if _lib is None:
+        if not os.path.exists(LIB_PATH):
+            raise ImportError("%s is missing — build it with `make -C fldr-vfi_amd/csrc` (or __graft_entry__.build())" % LIB_PATH)
+        l = ctypes.CDLL(LIB_PATH)
+        for name, (res, args) in _SIGNATURES.items():
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = res, args
+        for which, cls in enumerate((Format, Frame, IO, SessionConfig)):
+            if l.fldr_video_sizeof(which) != ctypes.sizeof(cls):
+                raise ImportError("%s: sizeof(%s) is %d in the library, %d in this binding" % (LIB_PATH, cls.__name__, l.fldr_video_sizeof(which),
+                                                                                              ctypes.sizeof(cls)))
+        if l.fldr_video_version() != VIDEO_VERSION:
+            raise ImportError("%s reports version %d, this binding is written for %d: rebuild it" % (LIB_PATH, l.fldr_video_version(), VIDEO_VERSION))
+        _lib = l
+    return _lib
+
+
+def _check(code, what):
+    if code != 0:
+        raise VideoError(what, code)
+
+
+# ---- geometry ---------------------------------------------------------------------------------------------------------------------
+def plane_shapes(layout, H, W):
+    """[(rows, row bytes)] of each plane of an H x W frame."""
+    ch, cw = (H + 1) // 2, (W + 1) // 2
+    return [(H, W), (ch, 2 * cw)] if _layout(layout) == 0 else [(H, W), (ch, cw), (ch, cw)]
+
+
+def _layout(layout):
+    return layout.layout if isinstance(layout, Format) else LAYOUTS[layout] if isinstance(layout, str) else int(layout)
+
+
+def frame_struct(planes):
+    """A Frame from a tuple of 2-D plane arrays (torch tensors or numpy arrays) with unit column stride."""
+    f = Frame()
+    for p, a in enumerate(planes):
+        if torch.is_tensor(a):
+            assert a.dtype == torch.uint8 and a.dim() == 2 and a.stride(1) == 1, "planes are 2-D uint8 with unit column stride"
+            f.plane[p], f.pitch[p] = a.data_ptr(), a.stride(0)
+        else:
+            assert a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1, "planes are 2-D uint8 with unit column stride"
+            f.plane[p], f.pitch[p] = a.ctypes.data, a.strides[0]
+    return f
+
+
+def empty_frame(layout, H, W, device):
+    return tuple(torch.empty(r, c, dtype=torch.uint8, device=device) for r, c in plane_shapes(layout, H, W))
+
+
+class NativeVideo:
+    """YUV forwards on a fldr_model.NativeModel (read-only: forwards on several streams, each with its own workspace, may run at once)."""
+
+    def __init__(self, native_model):
+        lib()
+        self.model = native_model
+        self.device = native_model.device
+
+    def workspace_bytes(self, H, W, n_t=1):
+        n = lib().fldr_video_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
+        if n < 0:
+            raise VideoError("fldr_video_workspace_bytes", int(n))
+        return int(n)
+
+    def workspace(self, H, W, n_t=1):
+        return torch.empty(self.workspace_bytes(H, W, n_t), dtype=torch.uint8, device=self.device)
+
+    def planar(self, ws, H, W, n_t=1):
+        """Views into a workspace after a forward: (pair [2,3,H,W], outputs [n_t][3,H,W]) — the planar BGR frames of the model."""
+        mb = fldr_model.lib().fldr_model_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
+        al = lambda v: (v + 255) // 256 * 256
+        pair = ws[al(mb):al(mb) + 6 * H * W].view(2, 3, H, W)
+        o = al(mb) + al(6 * H * W)
+        outs = [ws[o + k * al(3 * H * W):o + k * al(3 * H * W) + 3 * H * W].view(3, H, W) for k in range(n_t)]
+        return pair, outs
+
+    def forward_io(self, io, ws, stream=None):
+        """The raw call; returns the code without raising (tests of the error contract)."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.device)
+        return lib().fldr_video_forward(self.model._h, ctypes.byref(io), ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                        ws.numel() if ws is not None else 0, ctypes.c_void_p(st.cuda_stream))
+
+    def make_io(self, frames, t, in_format, out_format, outs, H, W):
+        io = IO()
+        io.H, io.W = int(H), int(W)
+        io.in_format, io.out_format = in_format, out_format
+        for i, fr in enumerate(frames):
+            io.in_[i] = frame_struct(fr)
+        arr = (Frame * len(outs))(*[frame_struct(o) for o in outs])
+        io.n_t, io.t, io.out = len(outs), t.data_ptr(), ctypes.cast(arr, ctypes.POINTER(Frame))
+        io._keep = arr
+        return io
+
+    def forward(self, frames, t=0.5, in_format=None, out_format=None, outs=None, ws=None, stream=None):
+        """frames: (I0, I1), each a tuple of plane tensors in in_format; t: n_t values (a float32 device tensor is used in place: a
+        captured call reads it at replay).  -> the n_t output frames (`outs` when given; allocated packed otherwise)."""
+        in_format = in_format or Format()
+        out_format = out_format or Format(in_format.layout, in_format.matrix, in_format.range)
+        H, W = frames[0][0].shape
+        if torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous():
+            tt = t
+        else:
+            tt = torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device)
+        n_t = tt.numel()
+        if outs is None:
+            outs = [empty_frame(out_format, H, W, self.device) for _ in range(n_t)]
+        if ws is None:
+            ws = self.workspace(H, W, n_t)
+        io = self.make_io(frames, tt, in_format, out_format, outs, H, W)
+        _check(self.forward_io(io, ws, stream), "fldr_video_forward")
+        return outs
+
+
+class Session:
+    """fldr_video_session: host frames (tuples of numpy planes) pushed one by one; each push after the first returns n_t frames."""
+
+    def __init__(self, native_model, H, W, n_t=1, in_format=None, out_format=None, t=None):
+        in_format = in_format or Format()
+        out_format = out_format or Format(in_format.layout, in_format.matrix, in_format.range)
+        cfg = SessionConfig()
+        cfg.H, cfg.W, cfg.n_t, cfg.device = int(H), int(W), int(n_t), native_model.device.index or 0
+        cfg.in_format, cfg.out_format = in_format, out_format
+        if t is not None:
+            ta = (ctypes.c_float * n_t)(*[float(v) for v in t])
+            cfg.t = ctypes.cast(ta, ctypes.POINTER(ctypes.c_float))
+        self._h = ctypes.c_void_p()
+        self.model = native_model                                    # the session uses the model: keep it alive
+        _check(lib().fldr_video_session_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_video_session_create")
+        self.H, self.W, self.n_t, self.in_format, self.out_format = int(H), int(W), int(n_t), in_format, out_format
+        self._outs = [tuple(np.empty(s, np.uint8) for s in plane_shapes(out_format, H, W)) for _ in range(n_t)]
+
+    def push(self, frame):
+        """-> [] or a list of n_t output frames (tuples of numpy planes, fresh copies)."""
+        fr = frame_struct(frame)
+        outs = (Frame * self.n_t)(*[frame_struct(o) for o in self._outs])
+        n = ctypes.c_int(-1)
+        _check(lib().fldr_video_session_push(self._h, ctypes.byref(fr), outs, ctypes.byref(n)), "fldr_video_session_push")
+        self.last_n_out = n.value
+        return [tuple(p.copy() for p in o) for o in self._outs[:n.value]]
+
+    def reset(self):
+        _check(lib().fldr_video_session_reset(self._h), "fldr_video_session_reset")
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            lib().fldr_video_session_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -1,0 +1,294 @@
+// libfldr_video.so, host side: validation, the workspace layout, fldr_video_forward (input conversion -> one fldr_model_forward ->
+// n_t output conversions) and the session API for streams of host frames.  The only fldr_* functions called are those of
+// fldr_model.h.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "video_internal.h"
+
+using namespace fldr_video_impl;
+
+namespace {
+
+constexpr int64_t ALIGN = 256;
+int64_t align_up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
+
+int planes_of(int layout) { return layout == FLDR_VIDEO_NV12 ? 2 : 3; }
+
+int check_format(const fldr_video_format& f) {
+    if ((unsigned)f.layout > 1u || (unsigned)f.matrix > 1u || (unsigned)f.range > 1u) return FLDR_VIDEO_E_FORMAT;
+    for (int i = 0; i < 5; ++i) if (f.reserved[i]) return FLDR_VIDEO_E_FORMAT;
+    return 0;
+}
+
+// bytes per row of plane p of a frame of width W
+int64_t row_bytes(int layout, int p, int W) {
+    const int64_t cw = (W + 1) / 2;
+    return p == 0 ? W : (layout == FLDR_VIDEO_NV12 ? 2 * cw : cw);
+}
+
+int64_t rows_of(int p, int H) { return p == 0 ? H : (H + 1) / 2; }
+
+int check_frame(const fldr_video_frame& fr, int layout, int W) {
+    for (int p = 0; p < planes_of(layout); ++p) if (!fr.plane[p]) return FLDR_VIDEO_E_PLANE;
+    for (int p = 0; p < planes_of(layout); ++p) if (fr.pitch[p] < row_bytes(layout, p, W)) return FLDR_VIDEO_E_PITCH;
+    return 0;
+}
+
+// host-only checks of a forward's arguments (no model, no device)
+int validate_io(const fldr_video_io* io) {
+    if (!io) return FLDR_VIDEO_E_ARG;
+    if (io->H < 2 || io->W < 2 || io->n_t < 1 || !io->t || !io->out) return FLDR_VIDEO_E_ARG;
+    int rc = check_format(io->in_format);
+    if (!rc) rc = check_format(io->out_format);
+    for (int f = 0; f < 2 && !rc; ++f) rc = check_frame(io->in[f], io->in_format.layout, io->W);
+    for (int k = 0; k < io->n_t && !rc; ++k) rc = check_frame(io->out[k], io->out_format.layout, io->W);
+    return rc;
+}
+
+struct WsLayout { int64_t model, pair, out, total; };
+
+int64_t plan(const fldr_model* m, int H, int W, int n_t, WsLayout& L) {
+    if (!m || H < 2 || W < 2 || n_t < 1) return FLDR_VIDEO_E_ARG;
+    const int64_t mb = fldr_model_workspace_bytes(m, H, W, n_t);
+    if (mb < 0) return mb;
+    const int64_t fb = align_up(3ll * H * W);
+    L.model = 0;
+    L.pair = align_up(mb);
+    L.out = L.pair + align_up(6ll * H * W);
+    L.total = L.out + (int64_t)n_t * fb;
+    return L.total;
+}
+
+const YuvCoeffs& coeffs(const fldr_video_format& f) { return YUV_COEFFS[f.matrix][f.range]; }
+
+#define CK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
+
+}  // namespace
+
+extern "C" FLDR_VIDEO_API int fldr_video_version(void) { return FLDR_VIDEO_VERSION; }
+
+extern "C" FLDR_VIDEO_API const char* fldr_video_error_string(int code) {
+    switch (code) {
+    case 0: return "success";
+    case FLDR_VIDEO_E_ARG: return "fldr_video: bad argument";
+    case FLDR_VIDEO_E_FORMAT: return "fldr_video: unknown layout, matrix or range, or a non-zero reserved word";
+    case FLDR_VIDEO_E_PITCH: return "fldr_video: plane pitch shorter than its row";
+    case FLDR_VIDEO_E_PLANE: return "fldr_video: null plane pointer";
+    case FLDR_VIDEO_E_WORKSPACE: return "fldr_video: workspace missing, misaligned or too small";
+    case FLDR_VIDEO_E_DEVICE: return "fldr_video: no such device or out of memory";
+    default: return code > -100 && code < 0 ? fldr_model_error_string(code) : code > 0 ? hipGetErrorString((hipError_t)code)
+                                                                                      : "fldr_video: unknown error";
+    }
+}
+
+extern "C" FLDR_VIDEO_API int fldr_video_sizeof(int which) {
+    switch (which) {
+    case 0: return (int)sizeof(fldr_video_format);
+    case 1: return (int)sizeof(fldr_video_frame);
+    case 2: return (int)sizeof(fldr_video_io);
+    case 3: return (int)sizeof(fldr_video_session_config);
+    default: return FLDR_VIDEO_E_ARG;
+    }
+}
+
+extern "C" FLDR_VIDEO_API int64_t fldr_video_workspace_bytes(const fldr_model* m, int H, int W, int n_t) {
+    WsLayout L;
+    return plan(m, H, W, n_t, L);
+}
+
+extern "C" FLDR_VIDEO_API int fldr_video_forward(const fldr_model* m, const fldr_video_io* io, void* ws, int64_t ws_bytes, void* stream) {
+    CK(validate_io(io));
+    WsLayout L;
+    const int64_t total = plan(m, io->H, io->W, io->n_t, L);
+    if (total < 0) return (int)total;
+    if (!ws || ((uintptr_t)ws & (ALIGN - 1)) || ws_bytes < total) return FLDR_VIDEO_E_WORKSPACE;
+    const int H = io->H, W = io->W;
+    char* w = (char*)ws;
+    uint8_t* pair = (uint8_t*)(w + L.pair);
+    const hipStream_t s = (hipStream_t)stream;
+    std::vector<void*> planar((size_t)io->n_t);
+    for (int k = 0; k < io->n_t; ++k) planar[k] = w + L.out + (int64_t)k * align_up(3ll * H * W);
+    // the conversion writes the workspace only: if the model then refuses (a fault flag of an earlier call), no output is touched
+    CK(yuv420_to_planar_pair(io->in, io->in_format.layout, coeffs(io->in_format), pair, H, W, s));
+    fldr_model_io mio;
+    memset(&mio, 0, sizeof(mio));
+    mio.batch = 1; mio.H = H; mio.W = W; mio.input = FLDR_MODEL_IN_U8_PLANAR; mio.frames_u8 = pair;
+    mio.n_t = io->n_t; mio.t = io->t; mio.output = FLDR_MODEL_OUT_U8_PLANAR; mio.out = planar.data();
+    CK(fldr_model_forward(m, &mio, w + L.model, L.pair, stream));
+    for (int k = 0; k < io->n_t; ++k)
+        CK(planar_to_yuv420((const uint8_t*)planar[k], io->out[k], io->out_format.layout, coeffs(io->out_format), H, W, s));
+    return 0;
+}
+
+// ---- sessions -----------------------------------------------------------------------------------------------------------------
+struct fldr_video_session {
+    const fldr_model* model;
+    fldr_video_session_config cfg;
+    int device;
+    hipStream_t stream;
+    char* mem;                         // device: slot 0, slot 1, n_t outputs, t, workspace
+    uint8_t* pinned;                   // host: one input frame, n_t output frames (packed planes)
+    int64_t in_bytes, out_bytes, ws_bytes;
+    uint8_t* slot[2];
+    uint8_t* out_dev;
+    float* t_dev;
+    void* ws;
+    int prev;                          // slot holding the previous frame, -1 when none
+};
+
+namespace {
+
+struct DeviceGuard {                                      // make `dev` current, restore the caller's device on exit
+    int prev = -1;
+    int rc = 0;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev && hipSetDevice(dev) != hipSuccess) rc = FLDR_VIDEO_E_DEVICE;
+    }
+    ~DeviceGuard() { if (prev >= 0) { int cur = -1; if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev); } }
+};
+
+// packed planes of one frame (pitch = row bytes) starting at `base`
+fldr_video_frame packed(uint8_t* base, int layout, int H, int W) {
+    fldr_video_frame f;
+    memset(&f, 0, sizeof(f));
+    int64_t off = 0;
+    for (int p = 0; p < planes_of(layout); ++p) {
+        f.plane[p] = base + off;
+        f.pitch[p] = row_bytes(layout, p, W);
+        off += f.pitch[p] * rows_of(p, H);
+    }
+    return f;
+}
+
+int64_t frame_bytes(int layout, int H, int W) {
+    int64_t n = 0;
+    for (int p = 0; p < planes_of(layout); ++p) n += row_bytes(layout, p, W) * rows_of(p, H);
+    return n;
+}
+
+// rows of every plane from `src` (any pitches) to `dst` (any pitches), on the host
+void copy_planes(const fldr_video_frame& dst, const fldr_video_frame& src, int layout, int H, int W) {
+    for (int p = 0; p < planes_of(layout); ++p) {
+        const int64_t rb = row_bytes(layout, p, W), n = rows_of(p, H);
+        for (int64_t r = 0; r < n; ++r)
+            memcpy((uint8_t*)dst.plane[p] + r * dst.pitch[p], (const uint8_t*)src.plane[p] + r * src.pitch[p], (size_t)rb);
+    }
+}
+
+void release(fldr_video_session* s) {
+    DeviceGuard g(s->device);
+    if (s->stream) (void)hipStreamDestroy(s->stream);
+    if (s->mem) (void)hipFree(s->mem);
+    if (s->pinned) (void)hipHostFree(s->pinned);
+    (void)hipGetLastError();
+    delete s;
+}
+
+}  // namespace
+
+extern "C" FLDR_VIDEO_API int fldr_video_session_create(const fldr_model* m, const fldr_video_session_config* cfg, fldr_video_session** out) {
+    if (!cfg || !out) return FLDR_VIDEO_E_ARG;
+    *out = nullptr;
+    if (cfg->H < 2 || cfg->W < 2 || cfg->n_t < 1 || cfg->device < 0) return FLDR_VIDEO_E_ARG;
+    CK(check_format(cfg->in_format));
+    CK(check_format(cfg->out_format));
+    for (int i = 0; i < 4; ++i) if (cfg->reserved[i]) return FLDR_VIDEO_E_FORMAT;
+    if (!m) return FLDR_VIDEO_E_ARG;
+    const int H = cfg->H, W = cfg->W, n_t = cfg->n_t;
+    const int64_t wsb = fldr_video_workspace_bytes(m, H, W, n_t);
+    if (wsb < 0) return (int)wsb;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device >= ndev) { (void)hipGetLastError(); return FLDR_VIDEO_E_DEVICE; }
+    fldr_video_session* s = new (std::nothrow) fldr_video_session();
+    if (!s) return FLDR_VIDEO_E_DEVICE;
+    s->model = m;
+    s->cfg = *cfg;
+    s->cfg.t = nullptr;
+    s->device = cfg->device;
+    s->prev = -1;
+    s->in_bytes = align_up(frame_bytes(cfg->in_format.layout, H, W));
+    s->out_bytes = align_up(frame_bytes(cfg->out_format.layout, H, W));
+    s->ws_bytes = wsb;
+    DeviceGuard g(s->device);
+    if (g.rc) { delete s; return g.rc; }
+    const int64_t dev_total = 2 * s->in_bytes + n_t * s->out_bytes + align_up(4ll * n_t) + wsb;
+    const int64_t host_total = s->in_bytes + n_t * s->out_bytes;
+    if (hipMalloc((void**)&s->mem, (size_t)dev_total) != hipSuccess) { s->mem = nullptr; release(s); return FLDR_VIDEO_E_DEVICE; }
+    if (hipHostMalloc((void**)&s->pinned, (size_t)host_total, hipHostMallocDefault) != hipSuccess) { s->pinned = nullptr; release(s); return FLDR_VIDEO_E_DEVICE; }
+    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { s->stream = nullptr; release(s); return FLDR_VIDEO_E_DEVICE; }
+    s->slot[0] = (uint8_t*)s->mem;
+    s->slot[1] = s->slot[0] + s->in_bytes;
+    s->out_dev = s->slot[1] + s->in_bytes;
+    s->t_dev = (float*)(s->out_dev + n_t * s->out_bytes);
+    s->ws = (char*)s->t_dev + align_up(4ll * n_t);
+    std::vector<float> t((size_t)n_t);
+    for (int k = 0; k < n_t; ++k) t[k] = cfg->t ? cfg->t[k] : (float)(k + 1) / (float)(n_t + 1);
+    hipError_t e = hipMemcpyAsync(s->t_dev, t.data(), 4ull * n_t, hipMemcpyHostToDevice, s->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
+    if (e != hipSuccess) { release(s); return (int)e; }
+    *out = s;
+    return 0;
+}
+
+extern "C" FLDR_VIDEO_API int fldr_video_session_push(fldr_video_session* s, const fldr_video_frame* frame, const fldr_video_frame* host_outs,
+                                                      int* n_out) {
+    if (!s || !frame || !n_out) return FLDR_VIDEO_E_ARG;
+    *n_out = 0;
+    const fldr_video_session_config& c = s->cfg;
+    const int H = c.H, W = c.W, n_t = c.n_t;
+    CK(check_frame(*frame, c.in_format.layout, W));
+    if (s->prev >= 0) {
+        if (!host_outs) return FLDR_VIDEO_E_ARG;
+        for (int k = 0; k < n_t; ++k) CK(check_frame(host_outs[k], c.out_format.layout, W));
+    }
+    DeviceGuard g(s->device);
+    if (g.rc) return g.rc;
+    const int cur = s->prev == 0 ? 1 : 0;                          // the slot not holding the previous frame
+    copy_planes(packed(s->pinned, c.in_format.layout, H, W), *frame, c.in_format.layout, H, W);
+    hipError_t e = hipMemcpyAsync(s->slot[cur], s->pinned, (size_t)s->in_bytes, hipMemcpyHostToDevice, s->stream);
+    int rc = e == hipSuccess ? 0 : (int)e;
+    const bool interp = s->prev >= 0;
+    uint8_t* out_host = s->pinned + s->in_bytes;
+    if (!rc && interp) {
+        std::vector<fldr_video_frame> outs((size_t)n_t);
+        for (int k = 0; k < n_t; ++k) outs[k] = packed(s->out_dev + k * s->out_bytes, c.out_format.layout, H, W);
+        fldr_video_io io;
+        memset(&io, 0, sizeof(io));
+        io.H = H; io.W = W;
+        io.in_format = c.in_format;
+        io.in[0] = packed(s->slot[s->prev], c.in_format.layout, H, W);
+        io.in[1] = packed(s->slot[cur], c.in_format.layout, H, W);
+        io.out_format = c.out_format;
+        io.n_t = n_t; io.t = s->t_dev; io.out = outs.data();
+        rc = fldr_video_forward(s->model, &io, s->ws, s->ws_bytes, s->stream);
+        if (!rc) {
+            e = hipMemcpyAsync(out_host, s->out_dev, (size_t)(n_t * s->out_bytes), hipMemcpyDeviceToHost, s->stream);
+            if (e != hipSuccess) rc = (int)e;
+        }
+    }
+    e = hipStreamSynchronize(s->stream);
+    if (!rc && e != hipSuccess) rc = (int)e;
+    if (rc) { s->prev = -1; return rc; }                           // the held frame is not to be trusted
+    if (interp) {
+        for (int k = 0; k < n_t; ++k)
+            copy_planes(host_outs[k], packed(out_host + k * s->out_bytes, c.out_format.layout, H, W), c.out_format.layout, H, W);
+        *n_out = n_t;
+    }
+    s->prev = cur;
+    return 0;
+}
+
+extern "C" FLDR_VIDEO_API int fldr_video_session_reset(fldr_video_session* s) {
+    if (!s) return FLDR_VIDEO_E_ARG;
+    s->prev = -1;
+    return 0;
+}
+
+extern "C" FLDR_VIDEO_API void fldr_video_session_destroy(fldr_video_session* s) {
+    if (s) release(s);
+}

@@ -1,0 +1,14 @@
+// Internals shared by the two translation units of libfldr_video.so (hidden: -fvisibility=hidden + video/exports.map).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "fldr_video.h"
+#include "yuv_color.h"
+
+namespace fldr_video_impl {
+// Two YUV 4:2:0 frames (layout: FLDR_VIDEO_NV12 / I420) -> the planar uint8 pair [1,2,3,H,W] (plane c = BGR channel c), one launch.
+int yuv420_to_planar_pair(const fldr_video_frame in[2], int layout, const YuvCoeffs& k, uint8_t* pair, int H, int W, hipStream_t stream);
+// One planar uint8 frame [1,3,H,W] (BGR planes) -> one YUV 4:2:0 frame; bytes between a row's end and its pitch are not written.
+int planar_to_yuv420(const uint8_t* planar, const fldr_video_frame& out, int layout, const YuvCoeffs& k, int H, int W, hipStream_t stream);
+}  // namespace fldr_video_impl
