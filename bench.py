@@ -2,13 +2,21 @@
 """Headline benchmark: 4K (3840x2160) frame pairs interpolated per second (BASELINE.json metric, config 2:
 single 4K frame pair, 5-scale test path, t = 0.5) through the MI355X-native hot path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A step = one (frame pair, t) forward = the reference's `model_net(input_gpuList, t, normInput=pyramid, ...)` call
 (main.py:867) with the 6-level pyramid already resident in HBM.  Frame pairs are independent, so N ranks each
 interpolate their own pairs (weak scaling, no data-path collective); the only RCCL traffic is the barrier, a
 max-reduction of the elapsed time and a gather of the per-rank rates.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: set up, warm up, time the K steps, write --dump-outputs, print the line
+(the replay check of the captured graphs and the finite-frame / range check of the last frame guard the headline and stay).
+`--full` adds every other measurement after the timed region: single-stream latency (replayed and eager), the sustained
+rate, the loop enqueued eagerly, the uint8-in -> uint8-out leg, the varying-motion, ingest, multi-t (BASELINE config 3),
+fp16-mode and config-5 legs, the roofline of the dominant kernel and of the path, and the CPU baseline with the parity of
+the GPU frame against the oracle (~1 min more at 4K).  The --sustained-s / --*-steps / --multi-t-pairs / --no-cpu-baseline
+options size or skip those legs and have no effect without --full.
 
 `--gpus N` without a torch.distributed environment launches the N ranks itself (torch.distributed.run as a CHILD
 process, before this process touches the GPU) and exits with the child's code; inside a launch whose WORLD_SIZE
@@ -49,7 +57,9 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the timed region, run every other measurement and check of the benchmark too "
+                                                        "(latency, sustained rate, the informational legs, rooflines, CPU baseline and parity)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and its parity check")
     ap.add_argument("--streams", type=int, default=3,
                     help="independent frame-pair forwards kept in flight on separate HIP streams (1 = strictly serial)")
     ap.add_argument("--pairs", type=int, default=4, help="distinct frame pairs rotated through the timed loop (>= streams)")
@@ -451,9 +461,10 @@ def main():
         dt_local, out = timed_region()
     # --dump-outputs: the last timed step's frame, copied now (a graph replay returns its slot's buffer, which the legs below replay into)
     dumped = out.detach().cpu() if (gpu and a.dump_outputs and rank == 0) else None
-    # ---- sustained rate: the same loop for >= --sustained-s seconds (clocks settle, caches in steady state) ---
     dt = max_over_ranks(dt_local, device)
-    if gpu:
+    # ---- --full: single-stream latency; sustained rate: the same loop for >= --sustained-s seconds (clocks settle, caches in steady
+    # state); the same loop enqueued eagerly ---
+    if gpu and a.full:
         def one_at_a_time(fn, reps=6):                            # single-stream latency: a forward alone on the GPU, host waits for it
             for k in range(2):
                 fn(k * len(streams)); sync()
@@ -463,7 +474,7 @@ def main():
             return (time.perf_counter() - tl) / reps * 1e3
         latency_ms = one_at_a_time(step)
         latency_eager_ms = one_at_a_time(eager_step) if graph_state["on"] else latency_ms
-    if gpu and a.sustained_s > 0:
+    if gpu and a.full and a.sustained_s > 0:
         n_s = max(a.steps, int(a.sustained_s / max(dt / a.steps, 1e-5)) + 1)      # the same step count on every rank
         barrier()
         sync()
@@ -475,7 +486,7 @@ def main():
         d_s = max_over_ranks(time.perf_counter() - t1, device)
         sustained = {"seconds": round(d_s, 3), "steps": n_s, "ms_per_step": round(d_s / n_s * 1e3, 3),
                      "value": round(world * n_s / d_s, 3)}
-    if gpu and graph_state["on"]:                                  # the same loop enqueued eagerly, for the record (untimed for `value`)
+    if gpu and a.full and graph_state["on"]:                       # the same loop enqueued eagerly, for the record (untimed for `value`)
         n_e = max(a.steps, 40)
         barrier()
         sync()
@@ -497,14 +508,14 @@ def main():
         x_test = Hn.evaluate_dir(a.xtest_dir, multiple=a.xtest_multiple, model=model, args=args, device=device, rank=rank, world=world)
     pg_world = dist.get_world_size() if use_pg else 1
     if use_pg:
-        # Every collective of the run is behind us: release the other ranks NOW.  What follows on rank 0 (informational legs, roofline
-        # of the dominant kernel, the CPU baseline: ~1 min) involves no other rank, so none of them waits in a barrier that a slow or
-        # stuck leg would turn into a collective timeout over there.
+        # Every collective of the run is behind us: release the other ranks NOW.  What follows on rank 0 with --full (informational legs,
+        # roofline of the dominant kernel, the CPU baseline: ~1 min) involves no other rank, so none of them waits in a barrier that a
+        # slow or stuck leg would turn into a collective timeout over there.
         barrier()
         dist.destroy_process_group()
     if rank != 0:
         return
-    if gpu:
+    if gpu and a.full:
         # end-to-end on the device (informational, single stream): uint8 frames -> ingest kernels (normalise, reflect
         # pad, bicubic pyramid) -> forward -> rounded uint8 frame (fldr_frame_metrics)
         u8 = Hn.synthetic_pair(a.height, a.width, seed=my_pairs[0]).unsqueeze(0).to(device)
@@ -698,13 +709,15 @@ def main():
         if a.dry:
             res["dry"] = True
             res["data"] = "none (dry run: 1 ms sleep per step)"
-            if not a.no_cpu_baseline:                  # the leg itself runs in a dry launch too (rank 0, any world size), on a small pair
+            if a.full and not a.no_cpu_baseline:       # the leg itself runs in a dry launch too (rank 0, any world size), on a small pair
                 import fldr_harness as Hn
                 fr = Hn.frames_from_uint8(Hn.synthetic_pair(256, 256, seed=0))
                 res["cpu_baseline"], _ = cpu_baseline(fr, torch.tensor([[0.5]]), None, runs=1)
                 res["cpu_baseline"]["unit"] = "256x256 frame-pairs/s (dry run)"
         if gpu:
-            res["config"].update({"pyramid_bytes_per_pair": pyr_bytes, "single_stream_latency_ms": round(latency_ms, 3), "single_stream_latency_eager_ms": round(latency_eager_ms, 3),
+            res["config"]["pyramid_bytes_per_pair"] = pyr_bytes
+        if gpu and a.full:
+            res["config"].update({"single_stream_latency_ms": round(latency_ms, 3), "single_stream_latency_eager_ms": round(latency_eager_ms, 3),
                                   "ms_uint8_in_to_uint8_out_single_stream": round(dt_e2e * 1e3, 3)})
             if sustained:
                 res["sustained"] = sustained
@@ -743,9 +756,9 @@ def main():
                 with torch.no_grad():
                     g0 = Hn.interpolate(model, args, frames[0], t, pyramid=pyrs[0]).cpu()
                 res["cpu_baseline"], res["parity"] = cpu_baseline(frames[0].cpu(), t.cpu(), g0, runs=3 if world == 1 else 1)
-            if x_test is not None:
-                res["x_test"] = dict(x_test, dir=a.xtest_dir, multiple=a.xtest_multiple)
-                res.setdefault("parity", {})["x_test_psnr"] = x_test["psnr"]
+        if x_test is not None:                         # (--xtest-dir: with or without --full)
+            res["x_test"] = dict(x_test, dir=a.xtest_dir, multiple=a.xtest_multiple)
+            res.setdefault("parity", {})["x_test_psnr"] = x_test["psnr"]
         if dumped is not None:
             res["dump_outputs"] = {"dir": a.dump_outputs, "arrays": dump_outputs(a.dump_outputs, dumped), "seed": DUMP_SEED,
                                    "what": "rank 0's frame of the last timed step (pair %d, t=0.5), float64" % my_pairs[(a.steps - 1) % npairs]}

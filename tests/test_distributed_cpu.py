@@ -76,7 +76,7 @@ def _run_bench(extra, env_extra=None, timeout=300):
 def test_bench_self_launches_n_ranks_gloo_dry():
     """`python bench.py --gpus 2` with no torch.distributed environment starts the two ranks itself (the parent never
     touches the GPU); --backend gloo --dry runs the same launcher / barrier / MAX-reduction / JSON path on CPU."""
-    r, js = _run_bench(["--gpus", "2", "--backend", "gloo", "--dry", "--steps", "4", "--warmup", "1"])
+    r, js = _run_bench(["--gpus", "2", "--backend", "gloo", "--dry", "--steps", "4", "--warmup", "1", "--full"])
     assert r.returncode == 0, r.stdout + r.stderr
     assert len(js) == 1, r.stdout                          # rank 0 prints ONE line
     j = js[0]
@@ -84,9 +84,22 @@ def test_bench_self_launches_n_ranks_gloo_dry():
     assert len(j["config"]["per_rank_pairs_per_s"]) == 2
     assert j["value"] == pytest.approx(2 * 4 / (j["ms_per_step"] * 4e-3), rel=1e-3)
     assert j["value"] < sum(j["config"]["per_rank_pairs_per_s"]) * 1.001        # whole-job rate uses the MAX over ranks
-    # the CPU-baseline leg runs on rank 0 at ANY world size (after the other ranks were released), so a multi-GPU line is complete
+    # the CPU-baseline leg (--full) runs on rank 0 at ANY world size (after the other ranks were released), so a multi-GPU line is complete
     cb = j["cpu_baseline"]
     assert cb["kind"] == "port" and cb["runs"] == 1 and cb["value"] > 0 and cb["cores"] >= 1
+
+
+def test_bench_plain_run_is_the_headline_alone_gloo_dry():
+    """A plain `bench.py --gpus 1 --steps N --warmup W` runs set-up, warm-up and the timed steps and prints the headline line: none of
+    the legs that --full adds (here the CPU baseline, the one that a --dry run has) is run or reported."""
+    r, js = _run_bench(["--gpus", "1", "--backend", "gloo", "--dry", "--steps", "3", "--warmup", "1"])
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert len(js) == 1, r.stdout
+    j = js[0]
+    assert j["steps"] == 3 and j["warmup"] == 1 and j["higher_is_better"] is True and j["unit"] == "frame-pairs/s" and j["dry"] is True
+    assert j["value"] == pytest.approx(3 / (j["ms_per_step"] * 3e-3), rel=1e-3)
+    for k in ("cpu_baseline", "parity", "roofline", "sustained", "varying_motion", "incl_ingest", "multi_t", "fp16_conv_mode", "config5"):
+        assert k not in j, k
 
 
 def test_bench_launcher_failure_modes():
@@ -120,10 +133,10 @@ def test_bench_forced_process_group_world_size_one_gloo_dry():
 
 def test_bench_self_launches_eight_ranks_gloo_dry():
     """The N = 8 launch the driver makes on an 8-GPU node, rehearsed on CPU (gloo, --dry: launcher, rendezvous on 127.0.0.1, barriers,
-    MAX-reduction, all_gather of the per-rank rates, rank 0's complete JSON line with its CPU-baseline leg): eight ranks, eight disjoint
-    shards, one line.  No scaling curve has been measured on hardware."""
+    MAX-reduction, all_gather of the per-rank rates, rank 0's complete JSON line with its CPU-baseline leg of --full): eight ranks, eight
+    disjoint shards, one line.  No scaling curve has been measured on hardware."""
     import fldr_harness as Hn
-    r, js = _run_bench(["--gpus", "8", "--backend", "gloo", "--dry", "--steps", "4", "--warmup", "1"], timeout=600)
+    r, js = _run_bench(["--gpus", "8", "--backend", "gloo", "--dry", "--steps", "4", "--warmup", "1", "--full"], timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     assert len(js) == 1, r.stdout
     j = js[0]

@@ -2254,6 +2254,35 @@ def test_bench_dump_outputs_are_the_last_timed_frame(dev, model, clean_launcher,
     assert np.abs(frames[0] - ref).max() <= 1e-6, np.abs(frames[0] - ref).max()
 
 
+@pytest.mark.timeout(900)
+def test_bench_full_adds_every_leg_a_plain_run_skips(dev, clean_launcher):
+    """A plain `bench.py` line carries the headline and nothing that takes runs of its own; `--full` adds latency, the sustained rate, the
+    eager loop, the informational legs, the roofline and the CPU baseline with the parity of the GPU frame against the oracle.  540x960
+    with short legs (multi-t and config 5 run at 4K only)."""
+    import json
+    import os
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--height", "540", "--width", "960"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--sustained-s", "0.2", "--varying-motion-steps", "6", "--incl-ingest-steps", "6",
+                                                 "--fp16-mode-steps", "6"])):
+        r = clean_launcher(base + extra, env=env, timeout=420)
+        assert r["rc"] == 0, (name, r["stdout"][-2000:], r["stderr"][-4000:])
+        js = [json.loads(l) for l in r["stdout"].splitlines() if l.startswith("{")]
+        assert len(js) == 1 and js[0]["steps"] == 3 and js[0]["warmup"] == 1 and js[0]["value"] > 0, r["stdout"][-2000:]
+        lines[name] = js[0]
+    legs = ("sustained", "varying_motion", "incl_ingest", "fp16_conv_mode", "roofline", "cpu_baseline", "parity")
+    p, f = lines["plain"], lines["full"]
+    assert not [k for k in legs if k in p] and "single_stream_latency_ms" not in p["config"], p
+    assert p["config"]["hip_graphs"]["on"] and "eager_ms_per_step" not in p["config"]["hip_graphs"]
+    assert all(k in f for k in legs), sorted(f)
+    assert f["config"]["single_stream_latency_ms"] > 0 and f["config"]["hip_graphs"]["eager_ms_per_step"] > 0
+    assert f["roofline"]["launch_ms"] > 0 and f["cpu_baseline"]["value"] > 0
+    assert f["parity"]["max_abs_err"] < 2e-5 and f["parity"]["psnr_8bit_db"] > 90.0, f["parity"]
+
+
 def test_evaluate_dir_matches_per_frame_pipeline(hip, dev, model, tmp_path):
     """fldr_harness.evaluate_dir (the dataset-shaped entry: main.py:815-911) on a folder of PNG frames written here — one scene of
     5 frames, multiple = 4: the pair (0, 4) and its three intermediate targets — against the per-frame pipeline the other tests

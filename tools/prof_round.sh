@@ -21,5 +21,5 @@ timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $out/c
 timeout -k 10 200 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/corr_fetch -- python3 $root/tools/one_corr.py > /dev/null 2>&1
 timeout -k 10 200 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/corr_write -- python3 $root/tools/one_corr.py > /dev/null 2>&1
 echo "correlation done"
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_trace -- python3 $root/bench.py --no-cpu-baseline --steps 20 --warmup 3 --sustained-s 0 > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $out/bench_trace -- python3 $root/bench.py --full --no-cpu-baseline --steps 20 --warmup 3 --sustained-s 0 > $out/bench_under_rocprof.json 2> $out/bench_under_rocprof.err
 echo "bench trace done"

@@ -8,6 +8,6 @@ for tag in "$@"; do
   echo "== $tag" >> $out
   FLDR_LIB=tools/stamps/libfldr_$tag.so timeout -k 10 120 python tools/splat_acc64_probe.py >> $out 2>&1 || exit 1
 done
-python bench.py --steps 20 --warmup 5 > gpurun_out/bench_acc64v2.json 2> gpurun_out/bench_acc64v2.err || exit 1
+python bench.py --full --steps 20 --warmup 5 > $(dirname $out)/bench_acc64v2.json 2> $(dirname $out)/bench_acc64v2.err || exit 1
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/gpurun_out/prof_acc64 -o p -- python3 $GRAFT_REPO_ROOT/tools/splat_acc64_probe.py > $GRAFT_REPO_ROOT/gpurun_out/prof_acc64.log 2>&1

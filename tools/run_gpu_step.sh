@@ -5,7 +5,7 @@ out=gpurun_out/step.txt; : > $out
 if [ -n "$TESTS_K" ]; then timeout -k 10 900 python -m pytest tests -x -q -m gpu -k "$TESTS_K" > gpurun_out/t_step.txt 2>&1 || { tail -30 gpurun_out/t_step.txt; exit 1; }; fi
 for m in $MODES; do timeout -k 10 300 python tools/kernel_bench.py $m >> $out 2>&1 || exit 1; done
 if [ -n "$BENCH" ]; then
-  timeout -k 10 400 python bench.py --steps 40 --warmup 5 --no-cpu-baseline --fp16-mode-steps 0 --varying-motion-steps 0 --incl-ingest-steps 0 --multi-t-pairs 0 > gpurun_out/bench_step.json 2>> $out || exit 1
+  timeout -k 10 400 python bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --fp16-mode-steps 0 --varying-motion-steps 0 --incl-ingest-steps 0 --multi-t-pairs 0 > $(dirname $out)/bench_step.json 2>> $out || exit 1
   python - <<PY >> $out
 import json
 d=json.loads(open("gpurun_out/bench_step.json").read().strip().splitlines()[-1])
