@@ -309,21 +309,25 @@ def frames_from_uint8(u8):
     return ((u8.float() / 255) * 2 - 1).permute(1, 0, 2, 3).unsqueeze(0).contiguous()
 
 
+def texture(H, W, seed=0):
+    """The seeded multi-octave (1/f-like) random texture of the synthetic pairs: [1,3,H,W] fp32 stretched to exactly 0..1."""
+    g = torch.Generator().manual_seed(seed)
+    base = torch.zeros(1, 3, H, W)
+    for o in range(8):
+        s = 2 ** o
+        n = torch.rand(1, 3, -(-H // s) + 2, -(-W // s) + 2, generator=g)
+        if o:
+            n = F.interpolate(n, scale_factor=s, mode="bilinear", align_corners=False)
+        base += n[..., :H, :W] * (1.5 ** o)
+    return (base - base.amin()) / (base.amax() - base.amin())
+
+
 def synthetic_pair(H, W, seed=0, quadrant=False, device="cpu"):
     """Seeded synthetic uint8 frame pair (bench.py, tests, golden fixtures): a multi-octave (1/f-like) random
     texture, so that every pyramid level sees structure as in natural video; I1 is I0 shifted by (6,4) px, or by
     (+-12,+-8) px per quadrant to force occlusions/holes.  (5x5-smoothed white noise, the first recipe, has no
     content left below 1/8 resolution and the flow network then predicts meaningless +-40 px flows.)"""
-    g = torch.Generator().manual_seed(seed)
-    Hb, Wb = H + 64, W + 64
-    base = torch.zeros(1, 3, Hb, Wb)
-    for o in range(8):
-        s = 2 ** o
-        n = torch.rand(1, 3, -(-Hb // s) + 2, -(-Wb // s) + 2, generator=g)
-        if o:
-            n = F.interpolate(n, scale_factor=s, mode="bilinear", align_corners=False)
-        base += n[..., :Hb, :Wb] * (1.5 ** o)
-    base = (base - base.amin()) / (base.amax() - base.amin())
+    base = texture(H + 64, W + 64, seed)
     I0 = base[..., 32:H + 32, 32:W + 32]
     if not quadrant:
         I1 = base[..., 36:H + 36, 38:W + 38]
@@ -344,16 +348,8 @@ def synthetic_pair_varying(H, W, seed=0, device="cpu", zoom=1.012, rot_deg=0.25,
     non-rigid motion (2.5 % / 0.8 degrees: ~85 px at the corners, sources of one row spread over a dozen target rows).  (A global shift, synthetic_pair's
     default, is the easiest case for the scatter kernels: every row of sources lands on one row of targets.)"""
     import math
-    g = torch.Generator().manual_seed(seed)
     Hb, Wb = H + 128, W + 128
-    base = torch.zeros(1, 3, Hb, Wb)
-    for o in range(8):
-        s = 2 ** o
-        n = torch.rand(1, 3, -(-Hb // s) + 2, -(-Wb // s) + 2, generator=g)
-        if o:
-            n = F.interpolate(n, scale_factor=s, mode="bilinear", align_corners=False)
-        base += n[..., :Hb, :Wb] * (1.5 ** o)
-    base = (base - base.amin()) / (base.amax() - base.amin())
+    base = texture(Hb, Wb, seed)
     I0 = base[..., 64:H + 64, 64:W + 64]
     ys, xs = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
     cy, cx, z, a = (H - 1) / 2, (W - 1) / 2, zoom, math.radians(rot_deg)

@@ -249,7 +249,12 @@ def bwarp_mask_value(shape, flo):
 # network pieces  (fLDRnet.py)
 # --------------------------------------------------------------------------
 
+_CONV_F64 = False            # forward(conv_f64=True): every convolution accumulated in fp64 and rounded to fp32 once
+
+
 def _conv(w, name, x, stride=1, pad=1):
+    if _CONV_F64:
+        return F.conv2d(x.double(), w[name + ".weight"].double(), w[name + ".bias"].double(), stride=stride, padding=pad).float()
     return F.conv2d(x, w[name + ".weight"], w[name + ".bias"], stride=stride, padding=pad)
 
 
@@ -354,11 +359,22 @@ def synthesis_level0(w, flow_l, x_l, t, splat_fn=None, keep=None):
 
 
 def forward(w, pyramid, t_value, n_levels=None, identity_splat=False, keep=None,
-            out_size=(2160, 4096), conditioning=False):
+            out_size=(2160, 4096), conditioning=False, conv_f64=False):
     """DCTXVFInet.forward, test branch (fLDRnet.py:106-223).
 
     pyramid: list of [B,3,2,H/2^i,W/2^i] fp32 (B must be 1 for parity, SURVEY 8e);
-    t_value [B,1] fp32.  Returns fp64 [B,3,min(H,2160),min(W,4096)]."""
+    t_value [B,1] fp32.  Returns fp64 [B,3,min(H,2160),min(W,4096)].
+    conv_f64 (test diagnostic): the convolutions accumulate in fp64 and round once — another fp32-class result, independent of the CPU's
+    thread count and instruction set, whose distance from the default run measures how far fp32 rounding alone moves an output."""
+    global _CONV_F64
+    prev, _CONV_F64 = _CONV_F64, bool(conv_f64)
+    try:
+        return _forward(w, pyramid, t_value, n_levels, identity_splat, keep, out_size, conditioning)
+    finally:
+        _CONV_F64 = prev
+
+
+def _forward(w, pyramid, t_value, n_levels, identity_splat, keep, out_size, conditioning):
     n_levels = len(pyramid) if n_levels is None else n_levels
     keep = {} if keep is None else keep
     B = pyramid[0].shape[0]
