@@ -1343,6 +1343,14 @@ static int g_s2_xshift = -1;                     // -1: automatic (15 on wide im
 FLDR_HOOK int fldr_debug_s2_xshift(int v) { if (v >= -1 && v < S2_TW) g_s2_xshift = v; return g_s2_xshift; }
 static int g_s2_persistent = 1;
 FLDR_HOOK int fldr_debug_s2_persistent(int v) { if (v >= 0) g_s2_persistent = v; return g_s2_persistent; }
+// Upper bound on the persistent workgroups per XCD of every persistent launcher below (default 64: their LDS caps decide); lowering it
+// only deepens every workgroup's tile walk.
+static int g_s2_wgs_max = 64;
+FLDR_HOOK int fldr_debug_s2_wgs_per_xcd(int v) { if (v > 0) g_s2_wgs_max = v; return g_s2_wgs_max; }
+static inline int s2_wgs(int tiles_per_xcd, int cap) {
+    const int w = tiles_per_xcd < cap ? tiles_per_xcd : cap;
+    return w < g_s2_wgs_max ? w : g_s2_wgs_max;
+}
 
 template <int MT, int NMT, int PT, bool V4>
 static int s2_launch_pers2(S2Args& a, hipStream_t s, int lds_bytes) {
@@ -1375,7 +1383,7 @@ static int s2_launch_pers(S2Args& a, int N, hipStream_t s, int lds_bytes) {
     const int64_t total = (int64_t)N * a.n_tiles;
     if (total >= (1ll << 30)) return FLDR_E_SHAPE;
     a.tiles_per_xcd = (int)((total + 7) / 8);
-    a.wgs_per_xcd = a.tiles_per_xcd < 64 ? a.tiles_per_xcd : 64;
+    a.wgs_per_xcd = s2_wgs(a.tiles_per_xcd, 64);
     // 16-byte staging: the window start ix0 - 1 = 64 t - 2 x_shift - 2 is a multiple of 4 floats for odd shifts; rows and
     // planes must keep that alignment
     bool v4 = g_s2_vec4 && (a.x_shift & 1) && (a.Win & 3) == 0;
@@ -1437,7 +1445,7 @@ static int s2_launch_pers_spk(S2Args& a, int N, hipStream_t s, int lds_bytes, in
     if (total >= (1ll << 30)) return FLDR_E_SHAPE;
     a.tiles_per_xcd = (int)((total + 7) / 8);
     const int cap = (lds_bytes > 80 * 1024 ? 32 : 64) / pair;                // workgroups per XCD that fit: one or two per CU (a pair launch: shared by the two problems)
-    a.wgs_per_xcd = a.tiles_per_xcd < cap ? a.tiles_per_xcd : cap;
+    a.wgs_per_xcd = s2_wgs(a.tiles_per_xcd, cap);
     hipLaunchKernelGGL((conv4x4s2_pers_spk_kernel<MT, NMT, PT>), dim3(8 * a.wgs_per_xcd, pair), dim3(256), lds_bytes, s, a);
     FLDR_LAUNCH_RET();
 }
@@ -1459,7 +1467,7 @@ static int s2_launch_dma_spk(S2Args& a, int N, hipStream_t s, int lds_bytes, int
     if (total >= (1ll << 30)) return FLDR_E_SHAPE;
     a.tiles_per_xcd = (int)((total + 7) / 8);
     const int cap = 32 / pair;                                               // one workgroup per CU (a pair launch: shared by the two problems)
-    a.wgs_per_xcd = a.tiles_per_xcd < cap ? a.tiles_per_xcd : cap;
+    a.wgs_per_xcd = s2_wgs(a.tiles_per_xcd, cap);
     hipLaunchKernelGGL(conv4x4s2_dma_spk_kernel, dim3(8 * a.wgs_per_xcd, pair), dim3((4 + S2D_NLOAD) * 64), lds_bytes, s, a);
     FLDR_LAUNCH_RET();
 }

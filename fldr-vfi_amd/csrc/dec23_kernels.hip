@@ -697,6 +697,10 @@ extern "C" int fldr_dec23_prepack(const float* dec2_weight, float* wpack, fldr_s
     FLDR_LAUNCH_RET();
 }
 
+// Upper bound on the persistent workgroups per XCD (default 32, the LDS cap): lowering it only deepens every workgroup's tile walk.
+static int g_d23_wgs_max = 32;
+FLDR_HOOK int fldr_debug_dec23_wgs_per_xcd(int v) { if (v > 0) g_d23_wgs_max = v; return g_d23_wgs_max; }
+
 extern "C" int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
                                 const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
                                 double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, fldr_stream_t stream) {
@@ -730,6 +734,7 @@ extern "C" int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, cons
     a.total = a.per_sample * N;
     a.per_xcd = (a.total + 7) / 8;
     a.wgs_per_xcd = a.per_xcd < 32 ? a.per_xcd : 32;                     // one workgroup per CU (159 KB of LDS)
+    if (a.wgs_per_xcd > g_d23_wgs_max) a.wgs_per_xcd = g_d23_wgs_max;
     static std::atomic<uint64_t> attr64{0}, attr32{0}, attr8{0};
     if (out_f64) {
         if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&dec23_synth_kernel<double>), D23_LDS, attr64)) return e;

@@ -40,6 +40,8 @@ FLDR_API int fldr_debug_s2_persistent(int v);                               /* s
 FLDR_API int fldr_debug_s2_xshift(int v);                                   /* tile-grid shift of the persistent stride-2 kernel (output columns; -1: default) */
 FLDR_API int fldr_debug_s2_vec4(int v);                                     /* 16-byte staging loads of the persistent stride-2 kernel: 1 (default) / 0 */
 FLDR_API int fldr_debug_s2_dma(int v);                                      /* packed-source stride-2 encoders of 17..32 output channels: 1 (default) the LDS-DMA kernel, 0 the register-staged kernel; other: query */
+FLDR_API int fldr_debug_s2_wgs_per_xcd(int v);                              /* upper bound on the persistent workgroups per XCD of the persistent stride-2 encoders (default 64: the LDS caps rule); v > 0 sets, other: query.  Identical results */
+FLDR_API int fldr_debug_dec23_wgs_per_xcd(int v);                           /* upper bound on the persistent workgroups per XCD of fldr_dec23_synth (default 32: the LDS cap); v > 0 sets, other: query.  Identical results */
 FLDR_API int fldr_debug_dec3_xshift(int v);                                 /* tile-grid shift of dec3_synth (low-resolution columns; -1: default) */
 FLDR_API int fldr_debug_splat_group_fold(int v);                            /* fldr_softsplat_acc64, > 3 channels: 1 all channel groups of a tile in one workgroup where the map is large enough, 0 (default) one group per workgroup; other: query.  Same results */
 FLDR_API int fldr_debug_conv_occupancy(int* out4);                          /* occupancy query of the fp32-MFMA convolution kernels */

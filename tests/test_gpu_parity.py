@@ -1722,8 +1722,9 @@ def test_dec2_dec3_fused_producer_consumer_kernel(hip, dev, shape):
     """fldr_dec23_synth (round 5): dec2 = ReLU(conv3x3(cat(nearest-x2(dec1), enc1))) produced tile by tile in LDS by four waves while eight
     others run dec3's phase convolutions + fp64 softmax / blend on the previous tile — against fp64 torch (the bound of the matrix-core
     dec3 test, 3e-6) and against the two-kernel path (conv2d_spk + dec3_synth on the packed tensor): full and partial tiles, tiles at
-    every border, one-tile and many-tile workgroups, two samples, candidates that are strided views (as I0 / I1 are planes of the frame
-    pair tensor), the fp32 output."""
+    every border, two samples, candidates that are strided views (as I0 / I1 are planes of the frame pair tensor), the fp32 output.
+    At these shapes every workgroup does one tile; the walks of many tiles per workgroup (the producer-to-consumer handoff from one
+    tile to the next) are tested in tests/test_gpu_schedule.py::test_dec23_bits_independent_of_workgroups."""
     g = _gen(45)
     N, h, w = shape                                                          # half resolution (dec2 / enc1); dec1 at h/2 x w/2
     dec1 = torch.rand(N, 32, h // 2, w // 2, generator=g) * 1.5             # post-ReLU activations
