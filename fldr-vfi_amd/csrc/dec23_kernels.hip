@@ -100,10 +100,11 @@ struct D23Args {
     const float* t;                // [N]
     const float* poison;           // common.h: 0.0f, NaN once a ring wait expired (added to t: every frame written after the fault is NaN); + 64 bytes: the store sink of lanes without a pixel
     double T;
-    void* out;                     // [N,3,H,W] fp64 or fp32, or the rounded 8-bit frame [N,3,Hc,Wc] (cropped; Wc even)
+    void* out;                     // [N,3,H,W] fp64 or fp32, or the rounded 8-bit / 16-bit frame [N,3,Hc,Wc] (cropped; Wc even)
     int Hc, Wc;
     int N, H, W;                   // full resolution
     int tiles_x, per_sample, total, per_xcd, wgs_per_xcd;
+    int maxval;                    // the 16-bit rounded form only: the white level (1023)
 };
 
 // one 16-byte slot per lane from `g` (or the zero block) into 64 consecutive slots at `l`
@@ -372,7 +373,7 @@ __global__ __launch_bounds__(D23_THREADS) void dec23_synth_kernel(D23Args a) {
             // fp64 softmax / T + blend of the quad's row `ra` (final_kernels.hip, same arithmetic).  The softmax half needs no candidate; by
             // its end the candidates have returned, and that is where this wave's LDS-DMA pieces of tile k + 2 go: an LDS-DMA instruction
             // waits for every earlier vector-memory operation of its wave, so here it costs its own round trip only.
-            const bool live = c_li < h && c_lj < w && (sizeof(OUT) != 1 || (2 * c_li + ra < a.Hc && 2 * c_lj < a.Wc));
+            const bool live = c_li < h && c_lj < w && (sizeof(OUT) > 2 || (2 * c_li + ra < a.Hc && 2 * c_lj < a.Wc));
             // t and the fault poison (common.h) by SCALAR loads, spelled out: as ordinary loads of a may-alias pointer they became vector-memory
             // loads, and their first use — behind the LDS-DMA pieces the compiler sinks this code below — was an s_waitcnt vmcnt(0) that made
             // every consumer wave sit out the round trip of the pieces it had just issued
@@ -471,6 +472,20 @@ __global__ __launch_bounds__(D23_THREADS) void dec23_synth_kernel(D23Args a) {
                         unsigned char* o = reinterpret_cast<unsigned char*>(out) + ((int64_t)c_n * 3 + ch) * ((int64_t)a.Hc * a.Wc) + po8;
                         o = live ? o : reinterpret_cast<unsigned char*>(sink);
                         *reinterpret_cast<unsigned short*>(o) = (unsigned short)(q[0] | (q[1] << 8));
+                    } else if constexpr (sizeof(OUT) == 2) {
+                        // the rounded frame in 16-bit words (fldr_quantize_u16's arithmetic; white level maxval), cropped to Hc x Wc: two
+                        // pixels = one 32-bit store per channel — three stores behind the DMA pieces again.  A NaN (a poisoned frame) is 0.
+                        const double white = (double)a.maxval;
+                        unsigned q[2];
+#pragma unroll
+                        for (int rb = 0; rb < 2; ++rb) {
+                            double v = (res[rb] + 1.0) / 2.0;
+                            v = v == v ? (v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v)) : 0.0;
+                            q[rb] = (unsigned)(int)rint(v * white);
+                        }
+                        char* o = reinterpret_cast<char*>(out) + (((int64_t)c_n * 3 + ch) * ((int64_t)a.Hc * a.Wc) + po8) * 2;
+                        o = live ? o : sink;
+                        *reinterpret_cast<unsigned*>(o) = q[0] | (q[1] << 16);
                     } else {
                         char* o = reinterpret_cast<char*>(out + ((int64_t)c_n * 3 + ch) * HW) + (uint32_t)po * (uint32_t)sizeof(OUT);
                         o = live ? o : sink;
@@ -701,13 +716,15 @@ extern "C" int fldr_dec23_prepack(const float* dec2_weight, float* wpack, fldr_s
 static int g_d23_wgs_max = 32;
 FLDR_HOOK int fldr_debug_dec23_wgs_per_xcd(int v) { if (v > 0) g_d23_wgs_max = v; return g_d23_wgs_max; }
 
-extern "C" int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
-                                const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
-                                double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, fldr_stream_t stream) {
+// out_u16 (with its white level) is the fourth output form; its pairs of pixels are 32-bit stores
+static int d23_launch(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
+                      const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
+                      double* out_f64, float* out_f32, void* out_u8, uint16_t* out_u16, int maxval, int H_u8, int W_u8, int N, int H, int W, fldr_stream_t stream) {
     FLDR_CHECK_ARG(dec1_spk && enc1_spk && w2pack && bias2 && w3m && bias3 && cand && cand_bstride && cand_cstride && t && N > 0 && H > 0 && W > 0);
-    FLDR_CHECK_ARG((out_f64 != nullptr) + (out_f32 != nullptr) + (out_u8 != nullptr) == 1);
-    if (out_u8) {                                                        // the cropped 8-bit frame: pairs of pixels are stored together
-        FLDR_CHECK_ARG(H_u8 > 0 && W_u8 > 0 && H_u8 <= H && W_u8 <= W && (reinterpret_cast<uintptr_t>(out_u8) & 1) == 0);
+    FLDR_CHECK_ARG((out_f64 != nullptr) + (out_f32 != nullptr) + (out_u8 != nullptr) + (out_u16 != nullptr) == 1);
+    if (out_u16) { FLDR_CHECK_ARG(maxval >= 1 && maxval <= 65535); out_u8 = out_u16; }
+    if (out_u8) {                                                        // the cropped rounded frame: pairs of pixels are stored together
+        FLDR_CHECK_ARG(H_u8 > 0 && W_u8 > 0 && H_u8 <= H && W_u8 <= W && (reinterpret_cast<uintptr_t>(out_u8) & (out_u16 ? 3 : 1)) == 0);
         if (W_u8 & 1) return FLDR_E_SHAPE;
         if ((int64_t)H_u8 * W_u8 >= (1ll << 31)) return FLDR_E_SHAPE;
     }
@@ -725,7 +742,8 @@ extern "C" int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, cons
     }
     a.t = t; a.poison = fldr_status_poison_ptr(); a.T = T_param;
     if (!a.poison) return FLDR_E_STATUS;
-    a.out = out_f64 ? static_cast<void*>(out_f64) : (out_f32 ? static_cast<void*>(out_f32) : static_cast<void*>(out_u8));
+    a.out = out_f64 ? static_cast<void*>(out_f64) : (out_f32 ? static_cast<void*>(out_f32) : out_u8);
+    a.maxval = out_u16 ? maxval : 255;
     a.Hc = out_u8 ? H_u8 : H; a.Wc = out_u8 ? W_u8 : W;
     a.N = N; a.H = H; a.W = W;
     a.tiles_x = fldr_cdiv(W / 2, D23_TW);
@@ -735,16 +753,34 @@ extern "C" int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, cons
     a.per_xcd = (a.total + 7) / 8;
     a.wgs_per_xcd = a.per_xcd < 32 ? a.per_xcd : 32;                     // one workgroup per CU (159 KB of LDS)
     if (a.wgs_per_xcd > g_d23_wgs_max) a.wgs_per_xcd = g_d23_wgs_max;
-    static std::atomic<uint64_t> attr64{0}, attr32{0}, attr8{0};
+    static std::atomic<uint64_t> attr64{0}, attr32{0}, attr8{0}, attr16{0};
     if (out_f64) {
         if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&dec23_synth_kernel<double>), D23_LDS, attr64)) return e;
         hipLaunchKernelGGL((dec23_synth_kernel<double>), dim3(8 * a.wgs_per_xcd), dim3(D23_THREADS), D23_LDS, fldr_s(stream), a);
     } else if (out_f32) {
         if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&dec23_synth_kernel<float>), D23_LDS, attr32)) return e;
         hipLaunchKernelGGL((dec23_synth_kernel<float>), dim3(8 * a.wgs_per_xcd), dim3(D23_THREADS), D23_LDS, fldr_s(stream), a);
+    } else if (out_u16) {
+        if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&dec23_synth_kernel<uint16_t>), D23_LDS, attr16)) return e;
+        hipLaunchKernelGGL((dec23_synth_kernel<uint16_t>), dim3(8 * a.wgs_per_xcd), dim3(D23_THREADS), D23_LDS, fldr_s(stream), a);
     } else {
         if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&dec23_synth_kernel<uint8_t>), D23_LDS, attr8)) return e;
         hipLaunchKernelGGL((dec23_synth_kernel<uint8_t>), dim3(8 * a.wgs_per_xcd), dim3(D23_THREADS), D23_LDS, fldr_s(stream), a);
     }
     FLDR_LAUNCH_RET();
+}
+
+extern "C" int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
+                                const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
+                                double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, fldr_stream_t stream) {
+    return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, out_f64, out_f32, out_u8, nullptr, 0,
+                      H_u8, W_u8, N, H, W, stream);
+}
+
+extern "C" int fldr_dec23_synth_u16(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
+                                    const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
+                                    uint16_t* out_u16, int maxval, int H_u16, int W_u16, int N, int H, int W, fldr_stream_t stream) {
+    FLDR_CHECK_ARG(out_u16);
+    return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, nullptr, nullptr, nullptr, out_u16, maxval,
+                      H_u16, W_u16, N, H, W, stream);
 }

@@ -61,25 +61,44 @@ __global__ __launch_bounds__(256) void pyramid_bicubic_kernel(const float* __res
 #define IP_LW 72                              // LDS row: columns X0 - 4 ... X0 + 67 (16-byte aligned pieces)
 #define IP_LH 66                              // LDS rows: Y0 - 1 ... Y0 + 64
 #define IP_MAX_LEVELS 7                       // level 0 + factors 2 ... 64
-struct IpArgs {
-    const uint8_t* u8;
+// One body for both pixel containers (PIX = uint8_t: the 8-bit frames, divisor 255; PIX = uint16_t: 10 / 12-bit words, divisor `white` at
+// run time, values above it clamped to it).  Only the load and the normalisation differ; the staging, the level-0 stores and the bicubic
+// arithmetic are the same code, so the 8-bit instantiation gives the bits it always gave.
+template <typename PIX>
+struct IpArgsT {
+    const PIX* px;
     float* lv[IP_MAX_LEVELS];
     int n_levels, H, W, Hp, Wp;
+    unsigned maxval;                          // uint16_t only: the white level (1023)
 };
+typedef IpArgsT<uint8_t> IpArgs;
 __device__ __forceinline__ float ip_norm(uint8_t v) {
 #pragma clang fp contract(off)
     float f = (float)v / 255.0f;
     f = f * 2.0f;
     return f - 1.0f;
 }
-__global__ __launch_bounds__(256) void ingest_pyramid_kernel(IpArgs a) {
+// ip_norm's operation order with the divisor changed (an IEEE division: the bits of torch's u16.float() / maxval * 2 - 1)
+__device__ __forceinline__ float ip_norm16(unsigned v, unsigned maxval, float white) {
+#pragma clang fp contract(off)
+    float f = (float)min(v, maxval) / white;
+    f = f * 2.0f;
+    return f - 1.0f;
+}
+template <typename PIX>
+__global__ __launch_bounds__(256) void ingest_pyramid_kernel(IpArgsT<PIX> a) {
 #pragma clang fp contract(off)
     __shared__ __attribute__((aligned(16))) float tile[IP_LH * IP_LW];
     const int tid = threadIdx.x;
     const int X0 = blockIdx.x * IP_T, Y0 = blockIdx.y * IP_T;
     const int bct = blockIdx.z;                                          // ((b*3 + c)*2 + t) in the output
     const int t = bct & 1, c = (bct >> 1) % 3, b = bct / 6;
-    const uint8_t* src = a.u8 + ((int64_t)(b * 2 + t) * 3 + c) * a.H * a.W;
+    const PIX* src = a.px + ((int64_t)(b * 2 + t) * 3 + c) * a.H * a.W;
+    const float white = sizeof(PIX) == 2 ? (float)a.maxval : 255.0f;
+    auto norm = [&](PIX v) -> float {
+        if constexpr (sizeof(PIX) == 1) return ip_norm(v);
+        else return ip_norm16(v, a.maxval, white);
+    };
     // stage: one item = 4 columns of one row; level-0 coordinates clamped to the padded image (the pyramid's tap clamp), then
     // reflected into the frame (F.pad(mode='reflect'), main.py:848)
     for (int e = tid; e < IP_LH * (IP_LW / 4); e += 256) {
@@ -88,16 +107,22 @@ __global__ __launch_bounds__(256) void ingest_pyramid_kernel(IpArgs a) {
         const int sy = yc < a.H ? yc : 2 * (a.H - 1) - yc;
         const int x = X0 - 4 + 4 * q;
         float4 v;
-        if (x >= 0 && x + 3 < a.W && !(a.W & 3) && !((uintptr_t)a.u8 & 3)) {       // aligned dword of four frame pixels
-            const uint32_t w = *reinterpret_cast<const uint32_t*>(src + (int64_t)sy * a.W + x);
-            v = make_float4(ip_norm((uint8_t)w), ip_norm((uint8_t)(w >> 8)), ip_norm((uint8_t)(w >> 16)), ip_norm((uint8_t)(w >> 24)));
+        if (x >= 0 && x + 3 < a.W && !(a.W & 3) && !((uintptr_t)a.px & (4 * sizeof(PIX) - 1))) {   // aligned word of four frame pixels
+            if constexpr (sizeof(PIX) == 1) {
+                const uint32_t w = *reinterpret_cast<const uint32_t*>(src + (int64_t)sy * a.W + x);
+                v = make_float4(ip_norm((uint8_t)w), ip_norm((uint8_t)(w >> 8)), ip_norm((uint8_t)(w >> 16)), ip_norm((uint8_t)(w >> 24)));
+            } else {
+                const uint2 w = *reinterpret_cast<const uint2*>(src + (int64_t)sy * a.W + x);
+                v = make_float4(ip_norm16(w.x & 0xffffu, a.maxval, white), ip_norm16(w.x >> 16, a.maxval, white),
+                                ip_norm16(w.y & 0xffffu, a.maxval, white), ip_norm16(w.y >> 16, a.maxval, white));
+            }
         } else {
             float f[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const int xc = min(max(x + k, 0), a.Wp - 1);
                 const int sx = xc < a.W ? xc : 2 * (a.W - 1) - xc;
-                f[k] = ip_norm(src[(int64_t)sy * a.W + sx]);
+                f[k] = norm(src[(int64_t)sy * a.W + sx]);
             }
             v = make_float4(f[0], f[1], f[2], f[3]);
         }
@@ -144,10 +169,48 @@ extern "C" int fldr_ingest_pyramid_u8(const uint8_t* frames_u8, float* const* le
     if (Hp - H >= H || Wp - W >= W) return FLDR_E_SHAPE;            // reflect padding needs pad < size
     if ((Wp & 3) || (Hp & ((1 << (n_levels - 1)) - 1)) || (Wp & ((1 << (n_levels - 1)) - 1))) return FLDR_E_SHAPE;
     IpArgs a;
-    a.u8 = frames_u8; a.n_levels = n_levels; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp;
+    a.px = frames_u8; a.maxval = 255; a.n_levels = n_levels; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp;
     for (int i = 0; i < IP_MAX_LEVELS; ++i) { a.lv[i] = i < n_levels ? levels[i] : nullptr; FLDR_CHECK_ARG(i >= n_levels || levels[i]); }
     dim3 grid(fldr_cdiv(Wp, IP_T), fldr_cdiv(Hp, IP_T), B * 6);
-    hipLaunchKernelGGL(ingest_pyramid_kernel, grid, dim3(256), 0, fldr_s(stream), a);
+    hipLaunchKernelGGL(ingest_pyramid_kernel<uint8_t>, grid, dim3(256), 0, fldr_s(stream), a);
+    FLDR_LAUNCH_RET();
+}
+
+// The same launch for 16-bit containers: frames_u16 [B,2,3,H,W], values 0 .. maxval (1023 for 10-bit material; larger values are clamped
+// to maxval), v = u16 / maxval * 2 - 1.  Four pixels per 8-byte load where W % 4 == 0 and the base is 8-byte aligned.
+extern "C" int fldr_ingest_pyramid_u16(const uint16_t* frames_u16, float* const* levels, int n_levels, int maxval, int B, int H, int W, int Hp, int Wp,
+                                       fldr_stream_t stream) {
+    FLDR_CHECK_ARG(frames_u16 && levels && n_levels >= 1 && n_levels <= IP_MAX_LEVELS && B > 0 && H > 1 && W > 1 && Hp >= H && Wp >= W);
+    FLDR_CHECK_ARG(maxval >= 1 && maxval <= 65535 && (reinterpret_cast<uintptr_t>(frames_u16) & 1) == 0);
+    if (Hp - H >= H || Wp - W >= W) return FLDR_E_SHAPE;            // reflect padding needs pad < size
+    if ((Wp & 3) || (Hp & ((1 << (n_levels - 1)) - 1)) || (Wp & ((1 << (n_levels - 1)) - 1))) return FLDR_E_SHAPE;
+    IpArgsT<uint16_t> a;
+    a.px = frames_u16; a.maxval = (unsigned)maxval; a.n_levels = n_levels; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp;
+    for (int i = 0; i < IP_MAX_LEVELS; ++i) { a.lv[i] = i < n_levels ? levels[i] : nullptr; FLDR_CHECK_ARG(i >= n_levels || levels[i]); }
+    dim3 grid(fldr_cdiv(Wp, IP_T), fldr_cdiv(Hp, IP_T), B * 6);
+    hipLaunchKernelGGL(ingest_pyramid_kernel<uint16_t>, grid, dim3(256), 0, fldr_s(stream), a);
+    FLDR_LAUNCH_RET();
+}
+
+// ingest_kernel for 16-bit containers (level 0 only: the path of pyramids deeper than IP_MAX_LEVELS)
+__global__ __launch_bounds__(256) void ingest_u16_kernel(const uint16_t* __restrict__ u16, float* __restrict__ out, unsigned maxval,
+                                                         int H, int W, int Hp, int Wp) {
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y;
+    const int bct = blockIdx.z;                 // ((b*3 + c)*2 + t) in the output
+    if (x >= Wp) return;
+    const int t = bct & 1, c = (bct >> 1) % 3, b = bct / 6;
+    const int sx = x < W ? x : 2 * (W - 1) - x;
+    const int sy = y < H ? y : 2 * (H - 1) - y;
+    out[((int64_t)bct * Hp + y) * Wp + x] = ip_norm16(u16[(((int64_t)(b * 2 + t) * 3 + c) * H + sy) * W + sx], maxval, (float)maxval);
+}
+
+extern "C" int fldr_ingest_u16(const uint16_t* frames_u16, float* level0, int maxval, int B, int H, int W, int Hp, int Wp, fldr_stream_t stream) {
+    FLDR_CHECK_ARG(frames_u16 && level0 && B > 0 && H > 1 && W > 1 && Hp >= H && Wp >= W);
+    FLDR_CHECK_ARG(maxval >= 1 && maxval <= 65535 && (reinterpret_cast<uintptr_t>(frames_u16) & 1) == 0);
+    if (Hp - H >= H || Wp - W >= W) return FLDR_E_SHAPE;            // reflect padding needs pad < size
+    dim3 grid(fldr_cdiv(Wp, 256), Hp, B * 6);
+    hipLaunchKernelGGL(ingest_u16_kernel, grid, dim3(256), 0, fldr_s(stream), frames_u16, level0, (unsigned)maxval, H, W, Hp, Wp);
     FLDR_LAUNCH_RET();
 }
 
@@ -204,6 +267,32 @@ extern "C" int fldr_frame_metrics(const void* pred, int pred_is_f64, const uint8
     dim3 grid(fldr_cdiv(W, 256), H, B * 3);
     if (pred_is_f64) hipLaunchKernelGGL(metrics_kernel<double>, grid, dim3(256), 0, fldr_s(stream), (const double*)pred, target_u8_or_null, out_u8_or_null, sse_zeroed_or_null, H, W, Hp, Wp);
     else             hipLaunchKernelGGL(metrics_kernel<float>, grid, dim3(256), 0, fldr_s(stream), (const float*)pred, target_u8_or_null, out_u8_or_null, sse_zeroed_or_null, H, W, Hp, Wp);
+    FLDR_LAUNCH_RET();
+}
+
+
+// pred [B,3,Hp,Wp] (fp64 or fp32, [-1,1]) cropped to H x W -> uint16 [B,3,H,W]: rint(clamp((pred + 1) / 2, 0, 1) * maxval), half to even as
+// metrics_kernel; a NaN (a poisoned frame, common.h) gives 0.  The reference of dec23's 16-bit output form and its odd-width fallback.
+template <typename T>
+__global__ __launch_bounds__(256) void quantize_u16_kernel(const T* __restrict__ pred, uint16_t* __restrict__ out, double white,
+                                                           int H, int W, int Hp, int Wp) {
+#pragma clang fp contract(off)
+    const int x = blockIdx.x * 256 + threadIdx.x;
+    const int y = blockIdx.y;
+    const int bc = blockIdx.z;
+    if (x >= W) return;
+    double v = ((double)pred[((int64_t)bc * Hp + y) * Wp + x] + 1.0) / 2.0;
+    v = v == v ? (v < 0.0 ? 0.0 : (v > 1.0 ? 1.0 : v)) : 0.0;
+    out[((int64_t)bc * H + y) * W + x] = (uint16_t)(unsigned)(int)rint(v * white);
+}
+
+extern "C" int fldr_quantize_u16(const void* pred, int pred_is_f64, uint16_t* out_u16, int maxval, int B, int H, int W, int Hp, int Wp,
+                                 fldr_stream_t stream) {
+    FLDR_CHECK_ARG(pred && out_u16 && B > 0 && H > 0 && W > 0 && Hp >= H && Wp >= W && maxval >= 1 && maxval <= 65535);
+    FLDR_CHECK_ARG((reinterpret_cast<uintptr_t>(out_u16) & 1) == 0);
+    dim3 grid(fldr_cdiv(W, 256), H, B * 3);
+    if (pred_is_f64) hipLaunchKernelGGL(quantize_u16_kernel<double>, grid, dim3(256), 0, fldr_s(stream), (const double*)pred, out_u16, (double)maxval, H, W, Hp, Wp);
+    else             hipLaunchKernelGGL(quantize_u16_kernel<float>, grid, dim3(256), 0, fldr_s(stream), (const float*)pred, out_u16, (double)maxval, H, W, Hp, Wp);
     FLDR_LAUNCH_RET();
 }
 

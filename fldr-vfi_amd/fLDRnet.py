@@ -121,12 +121,13 @@ class DCTXVFInet(nn.Module):
         y = fldr_hip.conv2d_spk([pca if pca_spk is None else pca_spk], c0.weight, c0.bias, relu=True, want_f32=False, want_spk=True)
         return fldr_hip.conv2d_spk([y], c2.weight, c2.bias, relu=True, residual=pca, want_f32=True, want_spk=True)
 
-    def forward(self, input_gpuList, t_value, normInput=0, is_training=True, validation=False, epoch=0, frameT=None, *, emit_u8=None):
+    def forward(self, input_gpuList, t_value, normInput=0, is_training=True, validation=False, epoch=0, frameT=None, *, emit_u8=None, emit_u16=None):
         """input_gpuList: ignored placeholders (the reference overwrites them, fLDRnet.py:134); t_value [B,1];
         normInput: list of S_tst+1 tensors [B,3,2,H/2^i,W/2^i].  Returns (out fp64 [B,3,<=2160,<=4096], flow|None).
         emit_u8 = (H, W) (keyword-only, not in the reference's signature; fldr_harness.interpolate_u8): return the frame cropped to H x W and
         rounded to 8 bits straight from the synthesis kernel where the fused kernel runs (the fp64 frame is then never written); paths that
-        cannot honour it return the fp64 frame as ever — the caller looks at the dtype."""
+        cannot honour it return the fp64 frame as ever — the caller looks at the dtype.  emit_u16 = (H, W): the same in 16-bit words, white
+        level 1023 (10-bit code values; fldr_harness.interpolate_u16)."""
         if is_training:
             raise NotImplementedError("fldr-hip implements the inference (test) branch only")
         # fault flags of EARLIER forwards, read without a synchronisation (two host words the kernels store into): a drop-in caller that
@@ -179,7 +180,7 @@ class DCTXVFInet(nn.Module):
             state = {"key": (x_l[0], x_l[0]._version), "flow0": flow}
             self._pair_state = state if self.pair_cache else None
         out, refined = self.vfinet._synthesise(state["flow0"], x_l[0], t4, validation,
-                                               cache=state if self.pair_cache else None, u8_crop=emit_u8)
+                                               cache=state if self.pair_cache else None, u8_crop=emit_u8, u16_crop=emit_u16)
         return out[:, :, :self.output_size_test[0], :self.output_size_test[1]], refined                # :222
 
 
@@ -297,7 +298,7 @@ class DCTVFInet(nn.Module):
         return flow_l
 
     # ---- level 0 (fLDRnet.py:400-535) ------------------------------------------------------------
-    def _synthesise(self, flow_l, x_l, t_value, validation, cache=None, u8_crop=None):
+    def _synthesise(self, flow_l, x_l, t_value, validation, cache=None, u8_crop=None, u16_crop=None):
         a = self.args
         B = flow_l.shape[0]
         t4 = t_value.view(B, 1, 1, 1).float()
@@ -349,7 +350,7 @@ class DCTVFInet(nn.Module):
             # u8_crop = (H, W) (DCTXVFInet.forward's emit_u8): the cropped frame rounded to 8 bits comes straight out of the kernel's fp64
             # blend instead of the fp64 frame (run_on_your_images.py:100-109 needs nothing else)
             out = fldr_hip.dec23_synth(dec1p, enc1p, unet.dec2.weight, unet.dec2.bias, unet.dec3.weight, unet.dec3.bias, cands, t4, T,
-                                       u8_crop=u8_crop)
+                                       u8_crop=u8_crop, u16_crop=u16_crop)
         elif tuple(unet.dec3.weight.shape) == (6, 16, 3, 3) and H % 2 == 0 and W % 2 == 0:
             # dec3 + softmax/T + blend in one kernel; refine_out (6 full-resolution planes) is never stored
             out = fldr_hip.dec3_synth(unet.forward_until_dec2(srcs, packed_out=fldr_hip.DEC3_MFMA and fldr_hip.use_spk()),

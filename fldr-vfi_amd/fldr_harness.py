@@ -283,6 +283,22 @@ def interpolate_u8(model, args, frames_u8, t_value, target_u8=None, want_ssim=Fa
     return (img, (ps, ssim.cpu().tolist())) if ssim is not None else (img, ps)
 
 
+def interpolate_u16(model, args, frames_u16, t_value):
+    """interpolate_u8 for 10-bit material: uint16 frames [B,2,3,H,W] with values 0 .. 1023 -> fldr_ingest_pyramid_u16 -> forward -> the
+    rounded frame as uint16 [B,3,H,W] in the same code values, straight from the synthesis kernel for an even width
+    (fldr_dec23_synth_u16), through the fp64 frame and fldr_quantize_u16 otherwise."""
+    import fldr_hip
+    B, T, C, H, W = frames_u16.shape
+    with torch.no_grad():
+        pyr = fldr_hip.ingest_pyramid_u16(frames_u16, args.S_tst + 1)
+        direct = U8_DIRECT and W % 2 == 0 and hasattr(model, "vfinet")
+        pred, _ = model([None] * (args.S_tst + 1), t_value, normInput=pyr, is_training=False, validation=False,
+                        **({"emit_u16": (H, W)} if direct else {}))
+        if pred.dtype == torch.uint16:
+            return pred.contiguous()
+        return fldr_hip.quantize_u16(pred, min(H, pred.shape[2]), min(W, pred.shape[3]))
+
+
 def to_uint8_image(pred):
     """[3,H,W] in [-1,1] -> rounded [H,W,3] in [0,255] (main.py:885-894, utils.py:685-688)."""
     p = np.asarray(pred.detach().cpu() if torch.is_tensor(pred) else pred, dtype=np.float64)

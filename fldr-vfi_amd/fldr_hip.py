@@ -191,6 +191,12 @@ _SIGNATURES = {
     "fldr_dec23_synth": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.POINTER(ctypes.c_void_p),
                                         ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _c_float_p, ctypes.c_double, _c_float_p, _c_float_p,
                                         ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
+    "fldr_dec23_synth_u16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.POINTER(ctypes.c_void_p),
+                                            ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _c_float_p, ctypes.c_double, ctypes.c_void_p]
+                             + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
+    "fldr_ingest_u16": (ctypes.c_int, [ctypes.c_void_p, _c_float_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
+    "fldr_ingest_pyramid_u16": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int] * 7 + [ctypes.c_void_p]),
+    "fldr_quantize_u16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
     "fldr_ingest_u8": (ctypes.c_int, [ctypes.c_void_p, _c_float_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p]),
     "fldr_pyramid_bicubic": (ctypes.c_int, [_c_float_p, _c_float_p] + [ctypes.c_int] * 4 + [ctypes.c_void_p]),
     "fldr_ingest_pyramid_u8": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
@@ -1405,11 +1411,12 @@ def dec3_synth(d2, weight, bias, cands, t, T_param, out_dtype=torch.float64, wan
 DEC23_FUSED = os.environ.get("FLDR_DEC23", "1") != "0"
 
 
-def dec23_synth(dec1p, enc1p, w2, b2, w3, b3, cands, t, T_param, out_dtype=torch.float64, u8_crop=None):
+def dec23_synth(dec1p, enc1p, w2, b2, w3, b3, cands, t, T_param, out_dtype=torch.float64, u8_crop=None, u16_crop=None, maxval=1023):
     """PCARefineUNet.dec2 (on cat(nearest-x2(dec1), enc1), ReLU) + dec3 (on the nearest-x2 upsampled result) + softmax / T + blend
     (fLDRnet.py:638-643, 511-524) in one kernel.  dec1p: Spk [N,32,H/4,W/4]; enc1p: Spk [N,16,H/2,W/2]; w2 [16,48,3,3], w3 [6,16,3,3].
     u8_crop = (Hc, Wc) (Wc even): instead of the fp64 / fp32 frame, the frame cropped to Hc x Wc and rounded to 8 bits
-    (frame_metrics' arithmetic) as a uint8 tensor [N,3,Hc,Wc]."""
+    (frame_metrics' arithmetic) as a uint8 tensor [N,3,Hc,Wc].  u16_crop = (Hc, Wc) (Wc even): the same in 16-bit words with the white
+    level `maxval` (quantize_u16's arithmetic) as a uint16 tensor (fldr_dec23_synth_u16)."""
     N, c1, h4, w4 = dec1p.shape
     N2, c2, h, w = enc1p.shape
     assert isinstance(dec1p, Spk) and isinstance(enc1p, Spk) and N == N2 and c1 == 32 and c2 == 16 and h == 2 * h4 and w == 2 * w4
@@ -1442,6 +1449,15 @@ def dec23_synth(dec1p, enc1p, w2, b2, w3, b3, cands, t, T_param, out_dtype=torch
     t = t.reshape(N).contiguous().float()
     o64 = o32 = o8 = None
     hc = wc = 0
+    if u16_crop is not None:
+        assert u8_crop is None
+        hc, wc = int(u16_crop[0]), int(u16_crop[1])
+        assert 0 < hc <= H and 0 < wc <= W and wc % 2 == 0
+        out = torch.empty(N, 3, hc, wc, device=w2.device, dtype=torch.uint16)
+        _check(lib().fldr_dec23_synth_u16(ctypes.c_void_p(dec1p.ptr), ctypes.c_void_p(enc1p.ptr), _dev(w2p, "w2pack"), _dev(b2.detach(), "bias2"),
+                                          _dev(w3m, "w3m"), _dev(b3.detach(), "bias3"), ptrs, strides, cstrides, _dev(t, "t"), float(T_param),
+                                          _dev(out, "out", torch.uint16), int(maxval), hc, wc, N, H, W, _stream()), "fldr_dec23_synth_u16")
+        return out
     if u8_crop is not None:
         hc, wc = int(u8_crop[0]), int(u8_crop[1])
         assert 0 < hc <= H and 0 < wc <= W and wc % 2 == 0
@@ -1484,6 +1500,43 @@ def ingest_pyramid(frames_u8, n_levels=6):
         _check(lib().fldr_pyramid_bicubic(_dev(lv0, "level0"), _dev(lv, "level"), B * 6, Hp, Wp, f, _stream()), "fldr_pyramid_bicubic")
         pyr.append(lv)
     return pyr
+
+
+def ingest_pyramid_u16(frames_u16, n_levels=6, maxval=1023):
+    """uint16 frames [B,2,3,H,W] on the device (values 0 .. maxval; 10-bit material: 1023) -> the model's normInput list, as
+    ingest_pyramid: v / maxval * 2 - 1, reflect padding and the bicubic pyramid (fldr_ingest_pyramid_u16; deeper than 7 levels or a
+    padded width that is no multiple of 4: fldr_ingest_u16 + fldr_pyramid_bicubic per level)."""
+    B, T, C, H, W = frames_u16.shape
+    assert T == 2 and C == 3
+    div = (2 ** (n_levels - 1)) * 8
+    Hp, Wp = (H + div - 1) // div * div, (W + div - 1) // div * div
+    u16 = frames_u16 if frames_u16.is_contiguous() else frames_u16.contiguous()
+    if INGEST_FUSED and n_levels <= 7 and Wp % 4 == 0:
+        pyr = [torch.empty(B, 3, 2, Hp >> i, Wp >> i, device=u16.device, dtype=torch.float32) for i in range(n_levels)]
+        ptrs = (ctypes.c_void_p * n_levels)(*[p.data_ptr() for p in pyr])
+        _check(lib().fldr_ingest_pyramid_u16(_dev(u16, "frames", torch.uint16), ptrs, n_levels, int(maxval), B, H, W, Hp, Wp, _stream()),
+               "fldr_ingest_pyramid_u16")
+        return pyr
+    lv0 = torch.empty(B, 3, 2, Hp, Wp, device=u16.device, dtype=torch.float32)
+    _check(lib().fldr_ingest_u16(_dev(u16, "frames", torch.uint16), _dev(lv0, "level0"), int(maxval), B, H, W, Hp, Wp, _stream()), "fldr_ingest_u16")
+    pyr = [lv0]
+    for i in range(1, n_levels):
+        f = 2 ** i
+        lv = torch.empty(B, 3, 2, Hp // f, Wp // f, device=u16.device, dtype=torch.float32)
+        _check(lib().fldr_pyramid_bicubic(_dev(lv0, "level0"), _dev(lv, "level"), B * 6, Hp, Wp, f, _stream()), "fldr_pyramid_bicubic")
+        pyr.append(lv)
+    return pyr
+
+
+def quantize_u16(pred, H, W, maxval=1023):
+    """pred [B,3,Hp,Wp] (fp64/fp32, [-1,1]) -> uint16 [B,3,H,W]: the crop, rint(clip((x + 1) / 2, 0, 1) * maxval) (half to even)."""
+    B, C, Hp, Wp = pred.shape
+    assert C == 3 and pred.dtype in (torch.float64, torch.float32) and 0 < H <= Hp and 0 < W <= Wp
+    pred = pred.contiguous()
+    out = torch.empty(B, 3, H, W, device=pred.device, dtype=torch.uint16)
+    _check(lib().fldr_quantize_u16(_dev(pred, "pred", pred.dtype), int(pred.dtype == torch.float64), _dev(out, "out", torch.uint16), int(maxval),
+                                   B, H, W, Hp, Wp, _stream()), "fldr_quantize_u16")
+    return out
 
 
 def frame_metrics(pred, H, W, target_u8=None, want_u8=False):

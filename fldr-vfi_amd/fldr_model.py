@@ -17,12 +17,12 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfldr_model.so")
-MODEL_VERSION = 100               # include/fldr_model.h: FLDR_MODEL_VERSION
+MODEL_VERSION = 101               # include/fldr_model.h: FLDR_MODEL_VERSION
 MAX_LEVELS = 8
 
 F32, F64 = 0, 1
-IN_PYRAMID, IN_U8_PLANAR, IN_U8_INTERLEAVED = 0, 1, 2
-OUT_F64, OUT_U8_PLANAR, OUT_U8_INTERLEAVED = 0, 1, 2
+IN_PYRAMID, IN_U8_PLANAR, IN_U8_INTERLEAVED, IN_U10_PLANAR = 0, 1, 2, 3
+OUT_F64, OUT_U8_PLANAR, OUT_U8_INTERLEAVED, OUT_U10_PLANAR = 0, 1, 2, 3
 ORDERS = {"bgr": 0, "rgb": 1}
 E_ARG, E_SHAPE, E_STATUS, E_WORKSPACE, E_BATCH = -1, -2, -3, -10, -11
 E_IO, E_FORMAT, E_COMPRESSED, E_TRUNCATED, E_MISSING, E_TENSOR_SHAPE, E_DTYPE, E_DEVICE = -12, -13, -14, -15, -16, -17, -18, -19
@@ -245,6 +245,37 @@ class NativeModel:
             raise ValueError("out_layout must be 'planar' or 'hwc'")
         self._run(io, H, W, [out[k] for k in range(n_t)], ws, stream)
         return out
+
+    def interpolate_u10(self, frames, t=0.5, *, out="u10", ws=None, stream=None, pyramid_out=None):
+        """The 10-bit forms.  frames: uint16 [1,2,3,H,W] with code values 0 .. 1023 (FLDR_MODEL_IN_U10_PLANAR), or uint8 [1,2,3,H,W]
+        (8-bit in, 10-bit out).  out: "u10" -> uint16 [n_t,3,H,W] (FLDR_MODEL_OUT_U10_PLANAR), "u8" -> uint8 [n_t,3,H,W], "f64" -> the
+        fp64 frames [n_t,3,Hp,Wp].  pyramid_out as interpolate_u8."""
+        tt = t if (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()) else self._t(t)
+        n_t = tt.numel()
+        B, T, C, H, W = frames.shape
+        if T != 2 or C != 3 or frames.dtype not in (torch.uint16, torch.uint8):
+            raise ValueError("frames must be uint16 or uint8 [1,2,3,H,W]")
+        f = frames.contiguous()
+        io = IO()
+        io.batch, io.input, io.frames_u8 = B, (IN_U10_PLANAR if f.dtype == torch.uint16 else IN_U8_PLANAR), f.data_ptr()
+        io.n_t, io.t = n_t, tt.data_ptr()
+        for i, p in enumerate(pyramid_out or []):
+            assert p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()
+            io.pyramid[i] = p.data_ptr()
+        if out == "u10":
+            res = torch.empty(n_t, 3, H, W, dtype=torch.uint16, device=self.device)
+            io.output = OUT_U10_PLANAR
+        elif out == "u8":
+            res = torch.empty(n_t, 3, H, W, dtype=torch.uint8, device=self.device)
+            io.output = OUT_U8_PLANAR
+        elif out == "f64":
+            Hp, Wp = padded_size(H, W, self.test_scales)
+            res = torch.empty(n_t, 3, Hp, Wp, dtype=torch.float64, device=self.device)
+            io.output = OUT_F64
+        else:
+            raise ValueError("out must be 'u10', 'u8' or 'f64'")
+        self._run(io, H, W, [res[k] for k in range(n_t)], ws, stream)
+        return res
 
     def interpolate_multi(self, frames, t_values, pyramid=None, ws=None, stream=None):
         """fldr_harness.interpolate_multi through one native call: frames [1,3,2,H,W] in [-1,1] on the model's device (pyramid built

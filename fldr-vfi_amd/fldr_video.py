@@ -20,7 +20,7 @@ import fldr_model
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfldr_video.so")
-VIDEO_VERSION = 100               # include/fldr_video.h: FLDR_VIDEO_VERSION
+VIDEO_VERSION = 101               # include/fldr_video.h: FLDR_VIDEO_VERSION
 
 LAYOUTS = {"nv12": 0, "i420": 1}
 MATRICES = {"bt601": 0, "bt709": 1}
@@ -31,9 +31,25 @@ E_ARG, E_FORMAT, E_PITCH, E_PLANE, E_WORKSPACE, E_DEVICE = -100, -101, -102, -10
 class Format(ctypes.Structure):
     _fields_ = [("layout", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32), ("reserved", ctypes.c_int32 * 5)]
 
-    def __init__(self, layout="nv12", matrix="bt709", range="limited"):
+    # `reserved` mirrors the five words behind `range` of fldr_video_format: word 0 is `depth` (0 or 8: 8-bit samples, 10: 10-bit
+    # samples in 16-bit words — NV12 is then P010, I420 yuv420p10le), words 1 .. 4 are the header's reserved[4]
+    def __init__(self, layout="nv12", matrix="bt709", range="limited", depth=8):
         super().__init__(LAYOUTS.get(layout, layout) if isinstance(layout, str) else layout,
                          MATRICES[matrix] if isinstance(matrix, str) else matrix, RANGES[range] if isinstance(range, str) else range)
+        self.depth = depth
+
+    @property
+    def depth(self):
+        return int(self.reserved[0])
+
+    @depth.setter
+    def depth(self, v):
+        self.reserved[0] = int(v)
+
+    @property
+    def bits(self):
+        """8 or 10: the depth with the 0 alias resolved."""
+        return 10 if self.depth == 10 else 8
 
     @property
     def name(self):
@@ -102,9 +118,20 @@ def _check(code, what):
 
 # ---- geometry ---------------------------------------------------------------------------------------------------------------------
 def plane_shapes(layout, H, W):
-    """[(rows, row bytes)] of each plane of an H x W frame."""
+    """[(rows, samples per row)] of each plane of an H x W frame: bytes at depth 8, 16-bit words at depth 10 (plane_dtype)."""
     ch, cw = (H + 1) // 2, (W + 1) // 2
     return [(H, W), (ch, 2 * cw)] if _layout(layout) == 0 else [(H, W), (ch, cw), (ch, cw)]
+
+
+def _depth(fmt):
+    return fmt.bits if isinstance(fmt, Format) else 8
+
+
+def plane_dtype(fmt, numpy=False):
+    """The element type of a frame's planes: uint8, or uint16 for a Format of depth 10."""
+    if _depth(fmt) == 10:
+        return np.uint16 if numpy else torch.uint16
+    return np.uint8 if numpy else torch.uint8
 
 
 def _layout(layout):
@@ -116,16 +143,16 @@ def frame_struct(planes):
     f = Frame()
     for p, a in enumerate(planes):
         if torch.is_tensor(a):
-            assert a.dtype == torch.uint8 and a.dim() == 2 and a.stride(1) == 1, "planes are 2-D uint8 with unit column stride"
-            f.plane[p], f.pitch[p] = a.data_ptr(), a.stride(0)
+            assert a.dtype in (torch.uint8, torch.uint16) and a.dim() == 2 and a.stride(1) == 1, "planes are 2-D uint8 / uint16 with unit column stride"
+            f.plane[p], f.pitch[p] = a.data_ptr(), a.stride(0) * a.element_size()          # pitches are in bytes
         else:
-            assert a.dtype == np.uint8 and a.ndim == 2 and a.strides[1] == 1, "planes are 2-D uint8 with unit column stride"
+            assert a.dtype in (np.uint8, np.uint16) and a.ndim == 2 and a.strides[1] == a.itemsize, "planes are 2-D uint8 / uint16 with unit column stride"
             f.plane[p], f.pitch[p] = a.ctypes.data, a.strides[0]
     return f
 
 
 def empty_frame(layout, H, W, device):
-    return tuple(torch.empty(r, c, dtype=torch.uint8, device=device) for r, c in plane_shapes(layout, H, W))
+    return tuple(torch.empty(r, c, dtype=plane_dtype(layout), device=device) for r, c in plane_shapes(layout, H, W))
 
 
 class NativeVideo:
@@ -145,13 +172,17 @@ class NativeVideo:
     def workspace(self, H, W, n_t=1):
         return torch.empty(self.workspace_bytes(H, W, n_t), dtype=torch.uint8, device=self.device)
 
-    def planar(self, ws, H, W, n_t=1):
-        """Views into a workspace after a forward: (pair [2,3,H,W], outputs [n_t][3,H,W]) — the planar BGR frames of the model."""
+    def planar(self, ws, H, W, n_t=1, in_depth=8, out_depth=8):
+        """Views into a workspace after a forward: (pair [2,3,H,W], outputs [n_t][3,H,W]) — the planar BGR frames of the model, uint8, or
+        uint16 for the side whose format had depth 10."""
         mb = fldr_model.lib().fldr_model_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
         al = lambda v: (v + 255) // 256 * 256
-        pair = ws[al(mb):al(mb) + 6 * H * W].view(2, 3, H, W)
-        o = al(mb) + al(6 * H * W)
-        outs = [ws[o + k * al(3 * H * W):o + k * al(3 * H * W) + 3 * H * W].view(3, H, W) for k in range(n_t)]
+        bi, bo = (2 if in_depth == 10 else 1), (2 if out_depth == 10 else 1)
+        as_ = lambda x, b, shape: (x.view(torch.uint16) if b == 2 else x).view(shape)
+        pair = as_(ws[al(mb):al(mb) + 6 * H * W * bi], bi, (2, 3, H, W))
+        o = al(mb) + al(6 * H * W * bi)
+        st = al(3 * H * W * bo)
+        outs = [as_(ws[o + k * st:o + k * st + 3 * H * W * bo], bo, (3, H, W)) for k in range(n_t)]
         return pair, outs
 
     def forward_io(self, io, ws, stream=None):
@@ -175,7 +206,7 @@ class NativeVideo:
         """frames: (I0, I1), each a tuple of plane tensors in in_format; t: n_t values (a float32 device tensor is used in place: a
         captured call reads it at replay).  -> the n_t output frames (`outs` when given; allocated packed otherwise)."""
         in_format = in_format or Format()
-        out_format = out_format or Format(in_format.layout, in_format.matrix, in_format.range)
+        out_format = out_format or Format(in_format.layout, in_format.matrix, in_format.range, in_format.depth)
         H, W = frames[0][0].shape
         if torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous():
             tt = t
@@ -196,7 +227,7 @@ class Session:
 
     def __init__(self, native_model, H, W, n_t=1, in_format=None, out_format=None, t=None):
         in_format = in_format or Format()
-        out_format = out_format or Format(in_format.layout, in_format.matrix, in_format.range)
+        out_format = out_format or Format(in_format.layout, in_format.matrix, in_format.range, in_format.depth)
         cfg = SessionConfig()
         cfg.H, cfg.W, cfg.n_t, cfg.device = int(H), int(W), int(n_t), native_model.device.index or 0
         cfg.in_format, cfg.out_format = in_format, out_format
@@ -207,7 +238,7 @@ class Session:
         self.model = native_model                                    # the session uses the model: keep it alive
         _check(lib().fldr_video_session_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_video_session_create")
         self.H, self.W, self.n_t, self.in_format, self.out_format = int(H), int(W), int(n_t), in_format, out_format
-        self._outs = [tuple(np.empty(s, np.uint8) for s in plane_shapes(out_format, H, W)) for _ in range(n_t)]
+        self._outs = [tuple(np.empty(s, plane_dtype(out_format, numpy=True)) for s in plane_shapes(out_format, H, W)) for _ in range(n_t)]
 
     def push(self, frame):
         """-> [] or a list of n_t output frames (tuples of numpy planes, fresh copies)."""

@@ -463,6 +463,8 @@ namespace {
 
 #define CK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
 
+constexpr int U10_MAX = 1023;          // white level of the 10-bit forms
+
 fldr_spk_conv_desc spk_desc(const Conv& c, int N, int H, int W, int relu) {
     fldr_spk_conv_desc d;
     memset(&d, 0, sizeof(d));
@@ -502,6 +504,13 @@ int enqueue(const fldr_model* m, const fldr_model_io* io, char* ws, const Layout
         if (n <= 7) CK(fldr_ingest_pyramid_u8(io->frames_u8, lv, n, 1, L.H, L.W, Hp, Wp, s));
         else {
             CK(fldr_ingest_u8(io->frames_u8, lv[0], 1, L.H, L.W, Hp, Wp, s));
+            for (int i = 1; i < n; ++i) CK(fldr_pyramid_bicubic(lv[0], lv[i], 6, Hp, Wp, 1 << i, s));
+        }
+    } else if (io->input == FLDR_MODEL_IN_U10_PLANAR) {                 // fldr_hip.ingest_pyramid_u16
+        const uint16_t* u16 = (const uint16_t*)io->frames_u8;
+        if (n <= 7) CK(fldr_ingest_pyramid_u16(u16, lv, n, U10_MAX, 1, L.H, L.W, Hp, Wp, s));
+        else {
+            CK(fldr_ingest_u16(u16, lv[0], U10_MAX, 1, L.H, L.W, Hp, Wp, s));
             for (int i = 1; i < n; ++i) CK(fldr_pyramid_bicubic(lv[0], lv[i], 6, Hp, Wp, 1 << i, s));
         }
     } else if (io->input == FLDR_MODEL_IN_U8_INTERLEAVED) {
@@ -657,6 +666,19 @@ int enqueue(const fldr_model* m, const fldr_model_io* io, char* ws, const Layout
         const float* cand[6] = {w0, w1, it0, it1, I0, I1};
         const int64_t cb[6] = {0, 0, 0, 0, 0, 0};
         const int64_t cc[6] = {HW, HW, HW, HW, 2 * HW, 2 * HW};
+        if (io->output == FLDR_MODEL_OUT_U10_PLANAR) {                   // the 8-bit output's split: fused for even W, L.f64 + a rounding pass for odd W
+            uint16_t* o16 = (uint16_t*)io->out[k];
+            if (L.W & 1) {
+                double* f64 = (double*)(ws + L.f64);
+                CK(fldr_dec23_synth(ws + L.dec1p, ws + L.enc1p, m->w2pack, m->bias2, m->w3m, m->bias3, cand, cb, cc, t, m->T, f64, nullptr, nullptr,
+                                    0, 0, 1, Hp, Wp, s));
+                CK(fldr_quantize_u16(f64, 1, o16, U10_MAX, 1, L.H, L.W, Hp, Wp, s));
+            } else {
+                CK(fldr_dec23_synth_u16(ws + L.dec1p, ws + L.enc1p, m->w2pack, m->bias2, m->w3m, m->bias3, cand, cb, cc, t, m->T, o16, U10_MAX,
+                                        L.H, L.W, 1, Hp, Wp, s));
+            }
+            continue;
+        }
         double* o64 = nullptr;
         uint8_t* o8 = nullptr;
         uint8_t* planar = io->output == FLDR_MODEL_OUT_U8_PLANAR ? (uint8_t*)io->out[k] : (uint8_t*)(ws + L.u8);
@@ -678,7 +700,9 @@ int validate_io(const fldr_model* m, const fldr_model_io* io) {
     if (io->batch != 1) return FLDR_MODEL_E_BATCH;
     if (io->n_t < 1 || !io->t || !io->out) return FLDR_MODEL_E_ARG;
     for (int k = 0; k < io->n_t; ++k) if (!io->out[k]) return FLDR_MODEL_E_ARG;
-    if (io->output < FLDR_MODEL_OUT_F64 || io->output > FLDR_MODEL_OUT_U8_INTERLEAVED) return FLDR_MODEL_E_ARG;
+    if (io->output < FLDR_MODEL_OUT_F64 || io->output > FLDR_MODEL_OUT_U10_PLANAR) return FLDR_MODEL_E_ARG;
+    if (io->output == FLDR_MODEL_OUT_U10_PLANAR)                          // pairs of 16-bit pixels are stored as one word
+        for (int k = 0; k < io->n_t; ++k) if ((uintptr_t)io->out[k] & 3) return FLDR_MODEL_E_ARG;
     if ((unsigned)io->in_order > 1u || (unsigned)io->out_order > 1u) return FLDR_MODEL_E_ARG;
     if (io->output == FLDR_MODEL_OUT_U8_INTERLEAVED && io->out_pitch < 3ll * io->W) return FLDR_MODEL_E_ARG;
     switch (io->input) {
@@ -687,6 +711,9 @@ int validate_io(const fldr_model* m, const fldr_model_io* io) {
         break;
     case FLDR_MODEL_IN_U8_PLANAR:
         if (!io->frames_u8) return FLDR_MODEL_E_ARG;
+        break;
+    case FLDR_MODEL_IN_U10_PLANAR:
+        if (!io->frames_u8 || ((uintptr_t)io->frames_u8 & 1)) return FLDR_MODEL_E_ARG;
         break;
     case FLDR_MODEL_IN_U8_INTERLEAVED:
         if (!io->frame[0] || !io->frame[1]) return FLDR_MODEL_E_ARG;

@@ -20,21 +20,26 @@ int planes_of(int layout) { return layout == FLDR_VIDEO_NV12 ? 2 : 3; }
 
 int check_format(const fldr_video_format& f) {
     if ((unsigned)f.layout > 1u || (unsigned)f.matrix > 1u || (unsigned)f.range > 1u) return FLDR_VIDEO_E_FORMAT;
-    for (int i = 0; i < 5; ++i) if (f.reserved[i]) return FLDR_VIDEO_E_FORMAT;
+    if (f.depth != 0 && f.depth != 8 && f.depth != 10) return FLDR_VIDEO_E_FORMAT;
+    for (int i = 0; i < 4; ++i) if (f.reserved[i]) return FLDR_VIDEO_E_FORMAT;
     return 0;
 }
 
+bool deep(const fldr_video_format& f) { return f.depth == 10; }       // 16-bit words
+
 // bytes per row of plane p of a frame of width W
-int64_t row_bytes(int layout, int p, int W) {
-    const int64_t cw = (W + 1) / 2;
-    return p == 0 ? W : (layout == FLDR_VIDEO_NV12 ? 2 * cw : cw);
+int64_t row_bytes(int layout, int depth, int p, int W) {
+    const int64_t cw = (W + 1) / 2, b = depth == 10 ? 2 : 1;
+    return b * (p == 0 ? W : (layout == FLDR_VIDEO_NV12 ? 2 * cw : cw));
 }
 
 int64_t rows_of(int p, int H) { return p == 0 ? H : (H + 1) / 2; }
 
-int check_frame(const fldr_video_frame& fr, int layout, int W) {
-    for (int p = 0; p < planes_of(layout); ++p) if (!fr.plane[p]) return FLDR_VIDEO_E_PLANE;
-    for (int p = 0; p < planes_of(layout); ++p) if (fr.pitch[p] < row_bytes(layout, p, W)) return FLDR_VIDEO_E_PITCH;
+int check_frame(const fldr_video_frame& fr, const fldr_video_format& f, int W) {
+    const int layout = f.layout;
+    for (int p = 0; p < planes_of(layout); ++p) if (!fr.plane[p] || (deep(f) && ((uintptr_t)fr.plane[p] & 1))) return FLDR_VIDEO_E_PLANE;
+    for (int p = 0; p < planes_of(layout); ++p)
+        if (fr.pitch[p] < row_bytes(layout, f.depth, p, W) || (deep(f) && (fr.pitch[p] & 1))) return FLDR_VIDEO_E_PITCH;
     return 0;
 }
 
@@ -44,26 +49,28 @@ int validate_io(const fldr_video_io* io) {
     if (io->H < 2 || io->W < 2 || io->n_t < 1 || !io->t || !io->out) return FLDR_VIDEO_E_ARG;
     int rc = check_format(io->in_format);
     if (!rc) rc = check_format(io->out_format);
-    for (int f = 0; f < 2 && !rc; ++f) rc = check_frame(io->in[f], io->in_format.layout, io->W);
-    for (int k = 0; k < io->n_t && !rc; ++k) rc = check_frame(io->out[k], io->out_format.layout, io->W);
+    for (int f = 0; f < 2 && !rc; ++f) rc = check_frame(io->in[f], io->in_format, io->W);
+    for (int k = 0; k < io->n_t && !rc; ++k) rc = check_frame(io->out[k], io->out_format, io->W);
     return rc;
 }
 
-struct WsLayout { int64_t model, pair, out, total; };
+struct WsLayout { int64_t model, pair, out, out_stride, total; };
 
-int64_t plan(const fldr_model* m, int H, int W, int n_t, WsLayout& L) {
+// in_bytes / out_bytes: bytes per sample of the planar pair / outputs of THIS forward (the offsets); the total is always that of the
+// 16-bit regions, so one size serves every format (fldr_video_workspace_bytes has no format argument)
+int64_t plan(const fldr_model* m, int H, int W, int n_t, int in_bytes, int out_bytes, WsLayout& L) {
     if (!m || H < 2 || W < 2 || n_t < 1) return FLDR_VIDEO_E_ARG;
     const int64_t mb = fldr_model_workspace_bytes(m, H, W, n_t);
     if (mb < 0) return mb;
-    const int64_t fb = align_up(3ll * H * W);
     L.model = 0;
     L.pair = align_up(mb);
-    L.out = L.pair + align_up(6ll * H * W);
-    L.total = L.out + (int64_t)n_t * fb;
+    L.out = L.pair + align_up(6ll * H * W * in_bytes);
+    L.out_stride = align_up(3ll * H * W * out_bytes);
+    L.total = L.pair + align_up(12ll * H * W) + (int64_t)n_t * align_up(6ll * H * W);
     return L.total;
 }
 
-const YuvCoeffs& coeffs(const fldr_video_format& f) { return YUV_COEFFS[f.matrix][f.range]; }
+const YuvCoeffs& coeffs(const fldr_video_format& f) { return deep(f) ? YUV_COEFFS_10[f.matrix][f.range] : YUV_COEFFS[f.matrix][f.range]; }
 
 #define CK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
 
@@ -75,9 +82,9 @@ extern "C" FLDR_VIDEO_API const char* fldr_video_error_string(int code) {
     switch (code) {
     case 0: return "success";
     case FLDR_VIDEO_E_ARG: return "fldr_video: bad argument";
-    case FLDR_VIDEO_E_FORMAT: return "fldr_video: unknown layout, matrix or range, or a non-zero reserved word";
-    case FLDR_VIDEO_E_PITCH: return "fldr_video: plane pitch shorter than its row";
-    case FLDR_VIDEO_E_PLANE: return "fldr_video: null plane pointer";
+    case FLDR_VIDEO_E_FORMAT: return "fldr_video: unknown layout, matrix, range or depth, or a non-zero reserved word";
+    case FLDR_VIDEO_E_PITCH: return "fldr_video: plane pitch shorter than its row (or odd at depth 10)";
+    case FLDR_VIDEO_E_PLANE: return "fldr_video: null plane pointer (or an odd address at depth 10)";
     case FLDR_VIDEO_E_WORKSPACE: return "fldr_video: workspace missing, misaligned or too small";
     case FLDR_VIDEO_E_DEVICE: return "fldr_video: no such device or out of memory";
     default: return code > -100 && code < 0 ? fldr_model_error_string(code) : code > 0 ? hipGetErrorString((hipError_t)code)
@@ -97,13 +104,14 @@ extern "C" FLDR_VIDEO_API int fldr_video_sizeof(int which) {
 
 extern "C" FLDR_VIDEO_API int64_t fldr_video_workspace_bytes(const fldr_model* m, int H, int W, int n_t) {
     WsLayout L;
-    return plan(m, H, W, n_t, L);
+    return plan(m, H, W, n_t, 2, 2, L);
 }
 
 extern "C" FLDR_VIDEO_API int fldr_video_forward(const fldr_model* m, const fldr_video_io* io, void* ws, int64_t ws_bytes, void* stream) {
     CK(validate_io(io));
     WsLayout L;
-    const int64_t total = plan(m, io->H, io->W, io->n_t, L);
+    const bool in10 = deep(io->in_format), out10 = deep(io->out_format);
+    const int64_t total = plan(m, io->H, io->W, io->n_t, in10 ? 2 : 1, out10 ? 2 : 1, L);
     if (total < 0) return (int)total;
     if (!ws || ((uintptr_t)ws & (ALIGN - 1)) || ws_bytes < total) return FLDR_VIDEO_E_WORKSPACE;
     const int H = io->H, W = io->W;
@@ -111,16 +119,19 @@ extern "C" FLDR_VIDEO_API int fldr_video_forward(const fldr_model* m, const fldr
     uint8_t* pair = (uint8_t*)(w + L.pair);
     const hipStream_t s = (hipStream_t)stream;
     std::vector<void*> planar((size_t)io->n_t);
-    for (int k = 0; k < io->n_t; ++k) planar[k] = w + L.out + (int64_t)k * align_up(3ll * H * W);
+    for (int k = 0; k < io->n_t; ++k) planar[k] = w + L.out + (int64_t)k * L.out_stride;
     // the conversion writes the workspace only: if the model then refuses (a fault flag of an earlier call), no output is touched
-    CK(yuv420_to_planar_pair(io->in, io->in_format.layout, coeffs(io->in_format), pair, H, W, s));
+    if (in10) CK(yuv420_to_planar_pair10(io->in, io->in_format.layout, coeffs(io->in_format), (uint16_t*)pair, H, W, s));
+    else CK(yuv420_to_planar_pair(io->in, io->in_format.layout, coeffs(io->in_format), pair, H, W, s));
     fldr_model_io mio;
     memset(&mio, 0, sizeof(mio));
-    mio.batch = 1; mio.H = H; mio.W = W; mio.input = FLDR_MODEL_IN_U8_PLANAR; mio.frames_u8 = pair;
-    mio.n_t = io->n_t; mio.t = io->t; mio.output = FLDR_MODEL_OUT_U8_PLANAR; mio.out = planar.data();
+    mio.batch = 1; mio.H = H; mio.W = W; mio.input = in10 ? FLDR_MODEL_IN_U10_PLANAR : FLDR_MODEL_IN_U8_PLANAR; mio.frames_u8 = pair;
+    mio.n_t = io->n_t; mio.t = io->t; mio.output = out10 ? FLDR_MODEL_OUT_U10_PLANAR : FLDR_MODEL_OUT_U8_PLANAR; mio.out = planar.data();
     CK(fldr_model_forward(m, &mio, w + L.model, L.pair, stream));
-    for (int k = 0; k < io->n_t; ++k)
-        CK(planar_to_yuv420((const uint8_t*)planar[k], io->out[k], io->out_format.layout, coeffs(io->out_format), H, W, s));
+    for (int k = 0; k < io->n_t; ++k) {
+        if (out10) CK(planar_to_yuv420_10((const uint16_t*)planar[k], io->out[k], io->out_format.layout, coeffs(io->out_format), H, W, s));
+        else CK(planar_to_yuv420((const uint8_t*)planar[k], io->out[k], io->out_format.layout, coeffs(io->out_format), H, W, s));
+    }
     return 0;
 }
 
@@ -153,28 +164,29 @@ struct DeviceGuard {                                      // make `dev` current,
 };
 
 // packed planes of one frame (pitch = row bytes) starting at `base`
-fldr_video_frame packed(uint8_t* base, int layout, int H, int W) {
+fldr_video_frame packed(uint8_t* base, const fldr_video_format& fmt, int H, int W) {
+    const int layout = fmt.layout;
     fldr_video_frame f;
     memset(&f, 0, sizeof(f));
     int64_t off = 0;
     for (int p = 0; p < planes_of(layout); ++p) {
         f.plane[p] = base + off;
-        f.pitch[p] = row_bytes(layout, p, W);
+        f.pitch[p] = row_bytes(layout, fmt.depth, p, W);
         off += f.pitch[p] * rows_of(p, H);
     }
     return f;
 }
 
-int64_t frame_bytes(int layout, int H, int W) {
+int64_t frame_bytes(const fldr_video_format& fmt, int H, int W) {
     int64_t n = 0;
-    for (int p = 0; p < planes_of(layout); ++p) n += row_bytes(layout, p, W) * rows_of(p, H);
+    for (int p = 0; p < planes_of(fmt.layout); ++p) n += row_bytes(fmt.layout, fmt.depth, p, W) * rows_of(p, H);
     return n;
 }
 
 // rows of every plane from `src` (any pitches) to `dst` (any pitches), on the host
-void copy_planes(const fldr_video_frame& dst, const fldr_video_frame& src, int layout, int H, int W) {
-    for (int p = 0; p < planes_of(layout); ++p) {
-        const int64_t rb = row_bytes(layout, p, W), n = rows_of(p, H);
+void copy_planes(const fldr_video_frame& dst, const fldr_video_frame& src, const fldr_video_format& fmt, int H, int W) {
+    for (int p = 0; p < planes_of(fmt.layout); ++p) {
+        const int64_t rb = row_bytes(fmt.layout, fmt.depth, p, W), n = rows_of(p, H);
         for (int64_t r = 0; r < n; ++r)
             memcpy((uint8_t*)dst.plane[p] + r * dst.pitch[p], (const uint8_t*)src.plane[p] + r * src.pitch[p], (size_t)rb);
     }
@@ -211,8 +223,8 @@ extern "C" FLDR_VIDEO_API int fldr_video_session_create(const fldr_model* m, con
     s->cfg.t = nullptr;
     s->device = cfg->device;
     s->prev = -1;
-    s->in_bytes = align_up(frame_bytes(cfg->in_format.layout, H, W));
-    s->out_bytes = align_up(frame_bytes(cfg->out_format.layout, H, W));
+    s->in_bytes = align_up(frame_bytes(cfg->in_format, H, W));
+    s->out_bytes = align_up(frame_bytes(cfg->out_format, H, W));
     s->ws_bytes = wsb;
     DeviceGuard g(s->device);
     if (g.rc) { delete s; return g.rc; }
@@ -241,28 +253,28 @@ extern "C" FLDR_VIDEO_API int fldr_video_session_push(fldr_video_session* s, con
     *n_out = 0;
     const fldr_video_session_config& c = s->cfg;
     const int H = c.H, W = c.W, n_t = c.n_t;
-    CK(check_frame(*frame, c.in_format.layout, W));
+    CK(check_frame(*frame, c.in_format, W));
     if (s->prev >= 0) {
         if (!host_outs) return FLDR_VIDEO_E_ARG;
-        for (int k = 0; k < n_t; ++k) CK(check_frame(host_outs[k], c.out_format.layout, W));
+        for (int k = 0; k < n_t; ++k) CK(check_frame(host_outs[k], c.out_format, W));
     }
     DeviceGuard g(s->device);
     if (g.rc) return g.rc;
     const int cur = s->prev == 0 ? 1 : 0;                          // the slot not holding the previous frame
-    copy_planes(packed(s->pinned, c.in_format.layout, H, W), *frame, c.in_format.layout, H, W);
+    copy_planes(packed(s->pinned, c.in_format, H, W), *frame, c.in_format, H, W);
     hipError_t e = hipMemcpyAsync(s->slot[cur], s->pinned, (size_t)s->in_bytes, hipMemcpyHostToDevice, s->stream);
     int rc = e == hipSuccess ? 0 : (int)e;
     const bool interp = s->prev >= 0;
     uint8_t* out_host = s->pinned + s->in_bytes;
     if (!rc && interp) {
         std::vector<fldr_video_frame> outs((size_t)n_t);
-        for (int k = 0; k < n_t; ++k) outs[k] = packed(s->out_dev + k * s->out_bytes, c.out_format.layout, H, W);
+        for (int k = 0; k < n_t; ++k) outs[k] = packed(s->out_dev + k * s->out_bytes, c.out_format, H, W);
         fldr_video_io io;
         memset(&io, 0, sizeof(io));
         io.H = H; io.W = W;
         io.in_format = c.in_format;
-        io.in[0] = packed(s->slot[s->prev], c.in_format.layout, H, W);
-        io.in[1] = packed(s->slot[cur], c.in_format.layout, H, W);
+        io.in[0] = packed(s->slot[s->prev], c.in_format, H, W);
+        io.in[1] = packed(s->slot[cur], c.in_format, H, W);
         io.out_format = c.out_format;
         io.n_t = n_t; io.t = s->t_dev; io.out = outs.data();
         rc = fldr_video_forward(s->model, &io, s->ws, s->ws_bytes, s->stream);
@@ -276,7 +288,7 @@ extern "C" FLDR_VIDEO_API int fldr_video_session_push(fldr_video_session* s, con
     if (rc) { s->prev = -1; return rc; }                           // the held frame is not to be trusted
     if (interp) {
         for (int k = 0; k < n_t; ++k)
-            copy_planes(host_outs[k], packed(out_host + k * s->out_bytes, c.out_format.layout, H, W), c.out_format.layout, H, W);
+            copy_planes(host_outs[k], packed(out_host + k * s->out_bytes, c.out_format, H, W), c.out_format, H, W);
         *n_out = n_t;
     }
     s->prev = cur;

@@ -11,4 +11,8 @@ namespace fldr_video_impl {
 int yuv420_to_planar_pair(const fldr_video_frame in[2], int layout, const YuvCoeffs& k, uint8_t* pair, int H, int W, hipStream_t stream);
 // One planar uint8 frame [1,3,H,W] (BGR planes) -> one YUV 4:2:0 frame; bytes between a row's end and its pitch are not written.
 int planar_to_yuv420(const uint8_t* planar, const fldr_video_frame& out, int layout, const YuvCoeffs& k, int H, int W, hipStream_t stream);
+// The same two at depth 10: 16-bit words in the YUV planes (NV12 = P010, value << 6; I420 = yuv420p10le, value in the low bits; pitches in
+// bytes), planar uint16 BGR code values 0 .. 1023 on the model's side; k from YUV_COEFFS_10.
+int yuv420_to_planar_pair10(const fldr_video_frame in[2], int layout, const YuvCoeffs& k, uint16_t* pair, int H, int W, hipStream_t stream);
+int planar_to_yuv420_10(const uint16_t* planar, const fldr_video_frame& out, int layout, const YuvCoeffs& k, int H, int W, hipStream_t stream);
 }  // namespace fldr_video_impl

@@ -443,6 +443,12 @@ FLDR_API int fldr_dec23_prepack(const float* dec2_weight, float* wpack, fldr_str
 FLDR_API int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
                      const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
                      double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, fldr_stream_t stream);
+/* The same kernel with the rounded frame in 16-bit words: out_u16 [N,3,H_u16,W_u16] = rint(clamp((x + 1) / 2, 0, 1) * maxval) (half to even;
+ * maxval = 1023 for 10-bit material; a NaN — a poisoned frame — gives 0), the arithmetic of fldr_quantize_u16 straight from the fp64 blend.
+ * W_u16 even, out_u16 4-byte aligned (two pixels are one 32-bit store); every other argument as fldr_dec23_synth. */
+FLDR_API int fldr_dec23_synth_u16(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
+                     const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
+                     uint16_t* out_u16, int maxval, int H_u16, int W_u16, int N, int H, int W, fldr_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Callers either side of the path, on the device (the reference does these on the CPU).
@@ -462,11 +468,24 @@ FLDR_API int fldr_pyramid_bicubic(const float* level0, float* level_i, int plane
 FLDR_API int fldr_ingest_pyramid_u8(const uint8_t* frames_u8, float* const* levels, int n_levels, int B, int H, int W, int Hp, int Wp,
                            fldr_stream_t stream);
 
+/* The ingest for frames in 16-bit containers (10-bit video; 12-bit by the same call): frames_u16 [B,2,3,H,W], values 0 .. maxval (1023),
+ * x / maxval * 2 - 1 in fldr_ingest_u8's operation order; a value above maxval is clamped to it.  fldr_ingest_u16: level 0 only;
+ * fldr_ingest_pyramid_u16: every level in one launch, constraints and bits (given the level 0) of fldr_ingest_pyramid_u8, four pixels per
+ * 8-byte load where W % 4 == 0 and frames_u16 is 8-byte aligned.  With maxval = 255 on byte values: the bits of the 8-bit entries. */
+FLDR_API int fldr_ingest_u16(const uint16_t* frames_u16, float* level0, int maxval, int B, int H, int W, int Hp, int Wp, fldr_stream_t stream);
+FLDR_API int fldr_ingest_pyramid_u16(const uint16_t* frames_u16, float* const* levels, int n_levels, int maxval, int B, int H, int W, int Hp, int Wp,
+                            fldr_stream_t stream);
+
 /* main.py:885-911 on the device: crop pred [B,3,Hp,Wp] (fp64 if pred_is_f64 else fp32) to H x W, (x+1)/2 clipped to
  * [0,1] * 255, rounded half-to-even; optionally written as uint8 [B,3,H,W]; when target_u8 [B,3,H,W] is given,
  * sse[b] (zeroed by the caller) accumulates the squared error, so PSNR = 10 log10(255^2 * 3HW / sse[b]). */
 FLDR_API int fldr_frame_metrics(const void* pred, int pred_is_f64, const uint8_t* target_u8_or_null, uint8_t* out_u8_or_null,
                        double* sse_zeroed_or_null, int B, int H, int W, int Hp, int Wp, fldr_stream_t stream);
+
+/* The rounded frame in 16-bit words: pred [B,3,Hp,Wp] (fp64 if pred_is_f64 else fp32) cropped to H x W -> out_u16 [B,3,H,W] =
+ * rint(clamp((x + 1) / 2, 0, 1) * maxval), half to even, a NaN gives 0 (maxval = 1023: 10-bit code values). */
+FLDR_API int fldr_quantize_u16(const void* pred, int pred_is_f64, uint16_t* out_u16, int maxval, int B, int H, int W, int Hp, int Wp,
+                      fldr_stream_t stream);
 
 /* utils.ssim_bgr (utils.py:662-669; main.py:911) on the device: SSIM of the Y channel of two uint8 images [B,3,H,W]
  * in cv2 channel order (0 = B, 1 = G, 2 = R) — the rounded frame fldr_frame_metrics writes and the ground truth — with

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define FLDR_MODEL_VERSION 100           /* major*10000 + minor*100 + patch of this header */
+#define FLDR_MODEL_VERSION 101           /* major*10000 + minor*100 + patch of this header; 101: the 10-bit forms (IN / OUT_U10_PLANAR) */
 
 #define FLDR_MODEL_E_ARG        (-1)     /* bad argument: null pointer, non-positive size, unknown enum value, bad pitch */
 #define FLDR_MODEL_E_SHAPE      (-2)     /* frame size the model cannot take (reflect padding needs pad < size) */
@@ -68,10 +68,14 @@ typedef struct fldr_model_config {
 
 enum { FLDR_MODEL_IN_PYRAMID = 0,        /* pyramid[i]: fp32 [1,3,2,Hp>>i,Wp>>i], i <= S_tst (normInput of DCTXVFInet.forward) */
        FLDR_MODEL_IN_U8_PLANAR = 1,      /* frames_u8: [1,2,3,H,W] uint8 (I0, I1), as fldr_harness.interpolate_u8 takes them */
-       FLDR_MODEL_IN_U8_INTERLEAVED = 2  /* frame[0] = I0, frame[1] = I1: H rows of W 3-byte pixels, frame_pitch bytes apart */ };
+       FLDR_MODEL_IN_U8_INTERLEAVED = 2, /* frame[0] = I0, frame[1] = I1: H rows of W 3-byte pixels, frame_pitch bytes apart */
+       FLDR_MODEL_IN_U10_PLANAR = 3      /* frames_u8 points at [1,2,3,H,W] uint16 (2-byte aligned), 10-bit code values 0 .. 1023 normalised as
+                                            v / 1023 * 2 - 1; a value above 1023 is the caller's error and is read as 1023 */ };
 enum { FLDR_MODEL_OUT_F64 = 0,           /* out[k]: fp64 [1,3,Hp,Wp], the frame before DCTXVFInet.forward's crop view */
        FLDR_MODEL_OUT_U8_PLANAR = 1,     /* out[k]: uint8 [1,3,H,W], cropped and rounded (np.around of the de-normalised frame) */
-       FLDR_MODEL_OUT_U8_INTERLEAVED = 2 /* out[k]: H rows of W 3-byte pixels, out_pitch bytes apart */ };
+       FLDR_MODEL_OUT_U8_INTERLEAVED = 2,/* out[k]: H rows of W 3-byte pixels, out_pitch bytes apart */
+       FLDR_MODEL_OUT_U10_PLANAR = 3     /* out[k]: uint16 [1,3,H,W] (4-byte aligned), cropped and rounded to 10-bit code values:
+                                            rint(clip((x + 1) / 2, 0, 1) * 1023), half to even.  Any input form goes with any output form */ };
 enum { FLDR_MODEL_BGR = 0, FLDR_MODEL_RGB = 1 };   /* channel order of interleaved frames; plane c of the model = BGR channel c */
 
 #define FLDR_MODEL_MAX_LEVELS 8
@@ -84,7 +88,7 @@ typedef struct fldr_model_io {
     int32_t        input;                /* FLDR_MODEL_IN_* */
     const float*   pyramid[FLDR_MODEL_MAX_LEVELS];   /* IN_PYRAMID: the input; 8-bit inputs: NULL, or where the ingested levels are
                                                         written (instead of the workspace) for a caller that keeps them */
-    const uint8_t* frames_u8;
+    const uint8_t* frames_u8;            /* IN_U8_PLANAR; IN_U10_PLANAR: the uint16 frames through this pointer */
     const uint8_t* frame[2];
     int64_t        frame_pitch[2];       /* >= 3 W */
     int32_t        in_order;             /* FLDR_MODEL_BGR / FLDR_MODEL_RGB */

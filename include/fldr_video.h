@@ -1,6 +1,6 @@
 /*
- * fldr_video.h — video API of libfldr_video.so: frame interpolation on 8-bit YUV 4:2:0 frames (NV12 or I420), the formats decoders
- * hand out and encoders take back, on top of the C model API (include/fldr_model.h).
+ * fldr_video.h — video API of libfldr_video.so: frame interpolation on 8-bit and 10-bit YUV 4:2:0 frames (NV12 / P010, I420 /
+ * yuv420p10le), the formats decoders hand out and encoders take back, on top of the C model API (include/fldr_model.h).
  *
  * Plain C99; no HIP header is needed: the stream is a void* (a hipStream_t).  The library calls no fldr_* function but those of
  * fldr_model.h.
@@ -9,6 +9,12 @@
  * sample (i, j) at luma (2i, 2j + 1/2), the MPEG-2 / H.264 / HEVC default).  The input frames are converted to the 8-bit BGR frames a
  * caller would get by converting on the host, so a forward on a YUV pair is, bit for bit, the model's forward on those BGR frames.
  * Odd widths and heights are allowed; the chroma planes are ceil(W/2) x ceil(H/2).
+ * Depth 10 (fldr_video_format.depth): samples are little-endian 16-bit words, pitches stay in BYTES.  FLDR_VIDEO_NV12 is then P010 (the
+ * value in the high 10 bits, word = v << 6; the low 6 bits are ignored on input and written as zero), FLDR_VIDEO_I420 is yuv420p10le (the
+ * value in the low 10 bits; input words are masked with 0x3ff).  The same matrices, siting and fixed point with limited range Y 64 .. 940,
+ * C 64 .. 960; the model then runs on 10-bit BGR code values (FLDR_MODEL_IN_U10_PLANAR / OUT_U10_PLANAR), so the two extra bits go
+ * through the network.  in_format and out_format may differ in depth.  No transfer function is applied: PQ / HLG frames pass through as
+ * code values like any other.
  *
  * Contract:
  *   - fldr_video_forward enqueues on `stream`: the input conversion, one fldr_model_forward (8-bit planar in and out, n_t outputs
@@ -31,13 +37,13 @@
 extern "C" {
 #endif
 
-#define FLDR_VIDEO_VERSION 100           /* major*10000 + minor*100 + patch of this header */
+#define FLDR_VIDEO_VERSION 101           /* major*10000 + minor*100 + patch of this header; 101: fldr_video_format.depth (10-bit frames) */
 
 /* codes of this library: -100 and below, apart from the FLDR_MODEL_E_* range (-1 .. -99) */
 #define FLDR_VIDEO_E_ARG        (-100)   /* null pointer, bad size, n_t < 1, null model */
-#define FLDR_VIDEO_E_FORMAT     (-101)   /* unknown layout / matrix / range, or a non-zero reserved word */
-#define FLDR_VIDEO_E_PITCH      (-102)   /* a plane pitch shorter than its row */
-#define FLDR_VIDEO_E_PLANE      (-103)   /* a null plane pointer */
+#define FLDR_VIDEO_E_FORMAT     (-101)   /* unknown layout / matrix / range / depth, or a non-zero reserved word */
+#define FLDR_VIDEO_E_PITCH      (-102)   /* a plane pitch shorter than its row; depth 10: or an odd pitch */
+#define FLDR_VIDEO_E_PLANE      (-103)   /* a null plane pointer; depth 10: or an odd plane address */
 #define FLDR_VIDEO_E_WORKSPACE  (-104)   /* workspace null, not 256-byte aligned or smaller than fldr_video_workspace_bytes */
 #define FLDR_VIDEO_E_DEVICE     (-105)   /* session: no such device, or an allocation failed */
 
@@ -53,7 +59,8 @@ typedef struct fldr_video_format {
     int32_t layout;                      /* FLDR_VIDEO_NV12 / FLDR_VIDEO_I420 */
     int32_t matrix;                      /* FLDR_VIDEO_BT601 / FLDR_VIDEO_BT709 */
     int32_t range;                       /* FLDR_VIDEO_LIMITED / FLDR_VIDEO_FULL */
-    int32_t reserved[5];                 /* zero */
+    int32_t depth;                       /* 0 or 8: 8-bit samples; 10: 10-bit samples in 16-bit words (NV12 = P010, I420 = yuv420p10le) */
+    int32_t reserved[4];                 /* zero */
 } fldr_video_format;
 
 /* One frame: plane pointers (plane[2] unused for NV12) and their pitches in bytes (row r of plane p at plane[p] + r * pitch[p]). */
@@ -91,10 +98,13 @@ FLDR_VIDEO_API const char* fldr_video_error_string(int code);
  * FLDR_VIDEO_E_ARG otherwise */
 FLDR_VIDEO_API int         fldr_video_sizeof(int which);
 
-/* Bytes of workspace one forward of an H x W pair with n_t outputs needs: fldr_model_workspace_bytes, then the planar BGR pair
- * ([1,2,3,H,W] uint8, as FLDR_MODEL_IN_U8_PLANAR takes it), then n_t planar BGR outputs ([1,3,H,W] uint8 each, as
- * FLDR_MODEL_OUT_U8_PLANAR writes them), each part starting 256-byte aligned.  After a forward these planar frames stay there.
- * Negative on bad arguments. */
+/* Bytes of workspace one forward of an H x W pair with n_t outputs needs, whatever the formats: fldr_model_workspace_bytes, then the
+ * planar BGR pair ([1,2,3,H,W]: uint8 as FLDR_MODEL_IN_U8_PLANAR takes it, or uint16 for a 10-bit input), then n_t planar BGR outputs
+ * ([1,3,H,W] each: uint8, or uint16 for a 10-bit output), each part starting 256-byte aligned.  After a forward these planar frames stay
+ * there.  With 8-bit formats the pair is at align(model bytes) and output k at pair + align(6 H W) + k align(3 H W), as before the 10-bit
+ * formats existed; a 10-bit input puts the outputs behind align(12 H W), a 10-bit output spaces them align(6 H W) apart.  The size is that
+ * of the 16-bit regions, so it grew by 6 H W + 3 H W n_t bytes plus alignment over version 100: at 3840 x 2160 the part behind the model's
+ * 2,304.7 MB went from 49.8 + 24.9 n_t MB to 99.5 + 49.8 n_t MB.  Negative on bad arguments. */
 FLDR_VIDEO_API int64_t fldr_video_workspace_bytes(const fldr_model* model, int H, int W, int n_t);
 /* Enqueue one forward on `stream` (NULL = the null stream).  ws: device memory of at least fldr_video_workspace_bytes, 256-byte
  * aligned, not used by another forward in flight. */
