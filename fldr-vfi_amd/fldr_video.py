@@ -83,6 +83,15 @@ _SIGNATURES = {
 }
 EXPORTS = tuple(_SIGNATURES)
 _lib = None
+# libfldr_video_test.so (-DFLDR_TEST_HOOKS): the same sources + the converter hooks of include/fldr_video_test_hooks.h; tests only
+TEST_LIB_PATH = os.path.join(_HERE, "libfldr_video_test.so")
+_HOOK_SIGNATURES = {
+    "fldr_video_debug_to_planar": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.POINTER(Format), ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "fldr_video_debug_from_planar": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.POINTER(Format), ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "fldr_video_debug_last_path": (ctypes.c_int, []),
+}
+HOOKS = tuple(_HOOK_SIGNATURES)
+_hooks_lib = None
 
 
 class VideoError(RuntimeError):
@@ -114,6 +123,23 @@ def lib():
 def _check(code, what):
     if code != 0:
         raise VideoError(what, code)
+
+
+def test_hooks():
+    """The loaded libfldr_video_test.so (the product's sources + the fldr_video_debug_* converter hooks); tests only.  The product
+    library stays what lib() returns: the two are separate handles in one process."""
+    global _hooks_lib
+    if _hooks_lib is None:
+        if not os.path.exists(TEST_LIB_PATH):
+            raise ImportError("%s is missing — build it with `make -C fldr-vfi_amd/csrc` (or __graft_entry__.build())" % TEST_LIB_PATH)
+        l = ctypes.CDLL(TEST_LIB_PATH)
+        for name, (res, args) in list(_SIGNATURES.items()) + list(_HOOK_SIGNATURES.items()):
+            fn = getattr(l, name)
+            fn.restype, fn.argtypes = res, args
+        if l.fldr_video_version() != VIDEO_VERSION:
+            raise ImportError("%s reports version %d, this binding is written for %d: rebuild it" % (TEST_LIB_PATH, l.fldr_video_version(), VIDEO_VERSION))
+        _hooks_lib = l
+    return _hooks_lib
 
 
 # ---- geometry ---------------------------------------------------------------------------------------------------------------------
@@ -153,6 +179,42 @@ def frame_struct(planes):
 
 def empty_frame(layout, H, W, device):
     return tuple(torch.empty(r, c, dtype=plane_dtype(layout), device=device) for r, c in plane_shapes(layout, H, W))
+
+
+# ---- the converters alone (test build) ----------------------------------------------------------------------------------------------
+def _stream_ptr(device, stream):
+    st = stream if stream is not None else torch.cuda.current_stream(device)
+    return ctypes.c_void_p(st.cuda_stream)
+
+
+def debug_to_planar(frames, fmt, pair=None, stream=None):
+    """fldr_video_debug_to_planar: frames (I0, I1), each a tuple of device plane tensors in `fmt` (pitches from their strides) -> the
+    planar BGR pair [2,3,H,W] (uint8; uint16 at depth 10; `pair` when given).  Enqueues on torch's current stream."""
+    H, W = frames[0][0].shape
+    if pair is None:
+        pair = torch.empty(2, 3, H, W, dtype=plane_dtype(fmt), device=frames[0][0].device)
+    arr = (Frame * 2)(*[frame_struct(f) for f in frames])
+    _check(test_hooks().fldr_video_debug_to_planar(arr, ctypes.byref(fmt), ctypes.c_void_p(pair.data_ptr()), int(H), int(W),
+                                                   _stream_ptr(pair.device, stream)), "fldr_video_debug_to_planar")
+    return pair
+
+
+def debug_from_planar(planar, fmt, out=None, stream=None):
+    """fldr_video_debug_from_planar: a contiguous planar BGR device tensor [3,H,W] (uint8; uint16 at depth 10) -> one frame in `fmt`
+    (`out`: a tuple of plane tensors, pitches from their strides; allocated packed otherwise).  Enqueues on torch's current stream."""
+    _, H, W = planar.shape
+    assert planar.is_contiguous() and planar.dtype == plane_dtype(fmt)
+    if out is None:
+        out = empty_frame(fmt, H, W, planar.device)
+    fr = frame_struct(out)
+    _check(test_hooks().fldr_video_debug_from_planar(ctypes.c_void_p(planar.data_ptr()), ctypes.byref(fr), ctypes.byref(fmt), int(H), int(W),
+                                                     _stream_ptr(planar.device, stream)), "fldr_video_debug_from_planar")
+    return out
+
+
+def debug_last_path():
+    """1: the most recent converter launch of the test build took the wide-access (VEC) form, 0: the per-sample form, -1: none yet."""
+    return int(test_hooks().fldr_video_debug_last_path())
 
 
 class NativeVideo:

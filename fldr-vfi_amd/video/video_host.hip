@@ -304,3 +304,30 @@ extern "C" FLDR_VIDEO_API int fldr_video_session_reset(fldr_video_session* s) {
 extern "C" FLDR_VIDEO_API void fldr_video_session_destroy(fldr_video_session* s) {
     if (s) release(s);
 }
+
+// ---- converter hooks of the test build (include/fldr_video_test_hooks.h): the two converters alone, behind fldr_video_forward's checks ---
+#ifdef FLDR_TEST_HOOKS
+#include "fldr_video_test_hooks.h"
+
+extern "C" FLDR_VIDEO_API int fldr_video_debug_to_planar(const fldr_video_frame in[2], const fldr_video_format* format, void* pair, int H, int W,
+                                                         void* stream) {
+    if (!in || !format || !pair || ((uintptr_t)pair & (ALIGN - 1)) || H < 2 || W < 2) return FLDR_VIDEO_E_ARG;
+    CK(check_format(*format));
+    for (int f = 0; f < 2; ++f) CK(check_frame(in[f], *format, W));
+    const hipStream_t s = (hipStream_t)stream;
+    if (deep(*format)) return yuv420_to_planar_pair10(in, format->layout, coeffs(*format), (uint16_t*)pair, H, W, s);
+    return yuv420_to_planar_pair(in, format->layout, coeffs(*format), (uint8_t*)pair, H, W, s);
+}
+
+extern "C" FLDR_VIDEO_API int fldr_video_debug_from_planar(const void* planar, const fldr_video_frame* out_frame, const fldr_video_format* format,
+                                                           int H, int W, void* stream) {
+    if (!planar || !out_frame || !format || ((uintptr_t)planar & (ALIGN - 1)) || H < 2 || W < 2) return FLDR_VIDEO_E_ARG;
+    CK(check_format(*format));
+    CK(check_frame(*out_frame, *format, W));
+    const hipStream_t s = (hipStream_t)stream;
+    if (deep(*format)) return planar_to_yuv420_10((const uint16_t*)planar, *out_frame, format->layout, coeffs(*format), H, W, s);
+    return planar_to_yuv420((const uint8_t*)planar, *out_frame, format->layout, coeffs(*format), H, W, s);
+}
+
+extern "C" FLDR_VIDEO_API int fldr_video_debug_last_path(void) { return g_last_path; }
+#endif

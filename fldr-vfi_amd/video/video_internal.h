@@ -15,4 +15,8 @@ int planar_to_yuv420(const uint8_t* planar, const fldr_video_frame& out, int lay
 // bytes), planar uint16 BGR code values 0 .. 1023 on the model's side; k from YUV_COEFFS_10.
 int yuv420_to_planar_pair10(const fldr_video_frame in[2], int layout, const YuvCoeffs& k, uint16_t* pair, int H, int W, hipStream_t stream);
 int planar_to_yuv420_10(const uint16_t* planar, const fldr_video_frame& out, int layout, const YuvCoeffs& k, int H, int W, hipStream_t stream);
+#ifdef FLDR_TEST_HOOKS
+// libfldr_video_test.so only: the form the most recent of the four launchers above chose (1: VEC, 0: per-sample, -1: none launched yet)
+extern int g_last_path;
+#endif
 }  // namespace fldr_video_impl

@@ -13,6 +13,15 @@ namespace fldr_video_impl {
 #define VK_TX 64                 // threads along a row (x 4 pixels = 256 luma columns per block)
 #define VK_TY 4                  // rows per block
 
+// The test build (libfldr_video_test.so, include/fldr_video_test_hooks.h) records which form a launcher chose; the product compiles
+// VK_NOTE_PATH to nothing.
+#ifdef FLDR_TEST_HOOKS
+int g_last_path = -1;
+#define VK_NOTE_PATH(vec) (g_last_path = (vec) ? 1 : 0)
+#else
+#define VK_NOTE_PATH(vec) ((void)0)
+#endif
+
 __device__ __forceinline__ int clamp8(int v) { return min(max(v, 0), 255); }
 __device__ __forceinline__ uint32_t ld32(const uint8_t* p) { return *reinterpret_cast<const uint32_t*>(p); }
 __device__ __forceinline__ uint32_t ld16(const uint8_t* p) { return *reinterpret_cast<const uint16_t*>(p); }
@@ -132,6 +141,7 @@ int yuv420_to_planar_pair(const fldr_video_frame in[2], int layout, const YuvCoe
             if (p < np) vec = vec && al4(in[f].plane[p]) && (in[f].pitch[p] & 3) == 0;
         }
     a.dst = pair; a.H = H; a.W = W; a.k = k;
+    VK_NOTE_PATH(vec);
     const dim3 grid((((W + 3) >> 2) + VK_TX - 1) / VK_TX, (H + VK_TY - 1) / VK_TY, 2), block(VK_TX, VK_TY);
     if (layout == FLDR_VIDEO_NV12) {
         if (vec) hipLaunchKernelGGL((yuv420_to_planar_pair_kernel<FLDR_VIDEO_NV12, true>), grid, block, 0, stream, a);
@@ -244,6 +254,7 @@ int planar_to_yuv420(const uint8_t* planar, const fldr_video_frame& out, int lay
         if (p < np) vec = vec && al4(out.plane[p]) && (out.pitch[p] & 3) == 0;
     }
     a.src = planar; a.H = H; a.W = W; a.k = k;
+    VK_NOTE_PATH(vec);
     const int ch = (H + 1) >> 1;
     const dim3 grid((((W + 3) >> 2) + VK_TX - 1) / VK_TX, (ch + VK_TY - 1) / VK_TY, 1), block(VK_TX, VK_TY);
     if (layout == FLDR_VIDEO_NV12) {
@@ -376,6 +387,7 @@ int yuv420_to_planar_pair10(const fldr_video_frame in[2], int layout, const YuvC
             if (p < np) vec = vec && al8(in[f].plane[p]) && (in[f].pitch[p] & 7) == 0;
         }
     a.dst = pair; a.H = H; a.W = W; a.k = k;
+    VK_NOTE_PATH(vec);
     const dim3 grid((((W + 3) >> 2) + VK_TX - 1) / VK_TX, (H + VK_TY - 1) / VK_TY, 2), block(VK_TX, VK_TY);
     if (layout == FLDR_VIDEO_NV12) {
         if (vec) hipLaunchKernelGGL((yuv420_to_planar_pair10_kernel<FLDR_VIDEO_NV12, true>), grid, block, 0, stream, a);
@@ -485,6 +497,7 @@ int planar_to_yuv420_10(const uint16_t* planar, const fldr_video_frame& out, int
         if (p < np) vec = vec && al8(out.plane[p]) && (out.pitch[p] & 7) == 0;
     }
     a.src = planar; a.H = H; a.W = W; a.k = k;
+    VK_NOTE_PATH(vec);
     const int ch = (H + 1) >> 1;
     const dim3 grid((((W + 3) >> 2) + VK_TX - 1) / VK_TX, (ch + VK_TY - 1) / VK_TY, 1), block(VK_TX, VK_TY);
     if (layout == FLDR_VIDEO_NV12) {

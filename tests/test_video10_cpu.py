@@ -129,13 +129,11 @@ def test_example_builds_with_cc_and_knows_p10(tmp_path):
     assert u.returncode == 2
 
 
-def test_no_stale_half_packing_in_the_video_library():
-    """The 16-bit packing invites v_ashr_pk_* / v_cvt_pk_u16_* / v_cvt_pk_i16_* (video_kernels.hip, pack2h): none may be in the library,
-    and the 10-bit kernels are in it."""
+def _no_stale_half_packing(lib):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_resources as KR
     n, seen = 0, False
-    for blob in KR.code_objects(LIB):
+    for blob in KR.code_objects(lib):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(blob)
             f.flush()
@@ -143,8 +141,14 @@ def test_no_stale_half_packing_in_the_video_library():
         seen = seen or ("yuv420_to_planar_pair10_kernel" in txt and "planar_to_yuv420_10_kernel" in txt)
         n += len(re.findall(r"\bv_ashr_pk_\w+|\bv_cvt_pk_[ui]16_\w+", txt))
     assert seen and n == 0
-    for k in KR.kernels(LIB):
+    for k in KR.kernels(lib):
         assert k["scratch"] == 0 and k["vgpr_spills"] == 0, k
+
+
+def test_no_stale_half_packing_in_the_video_library():
+    """The 16-bit packing invites v_ashr_pk_* / v_cvt_pk_u16_* / v_cvt_pk_i16_* (video_kernels.hip, pack2h): none may be in the library,
+    and the 10-bit kernels are in it."""
+    _no_stale_half_packing(LIB)
 
 
 # ---- the colour definition --------------------------------------------------------------------------------------------------------
@@ -299,3 +303,45 @@ def test_unused_container_bits_do_not_reach_the_colour(layout):
     assert np.array_equal(HD.yuv420_to_bgr(*HD.unpack_planes(dirty, layout, 10), "bt709", "limited", 10), want)
     if layout == "nv12":
         assert all(int((p & 63).max()) == 0 for p in clean) and int(clean[0].max()) <= 1023 << 6
+
+
+# ---- the test build and the float64 definition at depth 10 --------------------------------------------------------------------------------
+def test_no_stale_half_packing_in_the_video_test_library():
+    """The same listing check on libfldr_video_test.so: it is the binary tests/test_gpu_video_convert.py executes."""
+    _no_stale_half_packing(os.path.join(PKG, "libfldr_video_test.so"))
+
+
+@pytest.mark.parametrize("mat,rng", FORMATS)
+def test_depth_10_is_within_the_derived_bound_of_the_float_definition(mat, rng):
+    """The integer oracle at depth 10 against the float64 definition written from the standard (tests/yuv_float_ref.py): pure triples (the
+    cube's six faces and a seeded million, as the round-trip test takes them) through the 4:4:4 forms, and full 4:2:0 noise frames in both
+    directions.  Bound, derived from the table: 0.5 + sum over the expression's coefficients of 2^-17 x the largest |operand| = 0.5151
+    (limited) / 0.5156 (full) to RGB, 0.5234 to YUV.  Measured maxima over the four formats: 4:4:4 0.5122 to RGB (BT.709 limited), 0.5140
+    to YUV (BT.601 limited); 4:2:0 noise 0.5092 to RGB, 0.5104 to YUV."""
+    import yuv_float_ref as F
+    k = HD.constants(mat, rng, 10)
+    up_bound, down_bound = 0.5 + F.coefficient_bound(k, 10, "to_rgb"), 0.5 + F.coefficient_bound(k, 10, "to_yuv")
+    assert 0.5 < up_bound < 0.516 and 0.5 < down_bound < 0.524
+    v = np.arange(1024, dtype=np.int64)
+    A, B = (a.ravel() for a in np.meshgrid(v, v, indexing="ij"))
+    trip = []
+    for fixed in (0, 1023):
+        Fx = np.full_like(A, fixed)
+        trip += [(Fx, A, B), (A, Fx, B), (A, B, Fx)]
+    g = np.random.default_rng(10)
+    trip.append(tuple(g.integers(0, 1024, 1000000) for _ in range(3)))
+    eu = ed = 0.0
+    for a, b, c in trip:
+        eu = max(eu, max(float(np.abs(i - F.clip(f, 10)).max()) for i, f in zip(HD.yuv444_to_rgb(a, b, c, mat, rng, 10), F.ycbcr_to_rgb(a, b, c, mat, rng, 10))))
+        ed = max(ed, max(float(np.abs(i - F.clip(f, 10)).max()) for i, f in zip(HD.rgb_to_yuv444(a, b, c, mat, rng, 10), F.rgb_to_ycbcr(a, b, c, mat, rng, 10))))
+    nu = nd = 0.0
+    for H, W in ((203, 301), (64, 96), (2, 2), (3, 5)):
+        g = np.random.default_rng(H * W + 10)
+        ch, cw = HD.chroma_size(H, W)
+        Y, U, V = (g.integers(0, 1024, s).astype(np.uint16) for s in ((H, W), (ch, cw), (ch, cw)))
+        nu = max(nu, float(np.abs(HD.yuv420_to_bgr(Y, U, V, mat, rng, 10) - F.yuv420_to_bgr(Y, U, V, mat, rng, 10)).max()))
+        bgr = g.integers(0, 1024, (3, H, W)).astype(np.uint16)
+        nd = max(nd, max(float(np.abs(i - f).max()) for i, f in zip(HD.bgr_to_yuv420(bgr, mat, rng, 10), F.bgr_to_yuv420(bgr, mat, rng, 10))))
+    print("10-bit, %s %s: max |integer - float| 4:4:4 %.4f to RGB, %.4f to YUV; 4:2:0 noise %.4f to RGB, %.4f to YUV; bounds %.4f, %.4f" % (
+        mat, rng, eu, ed, nu, nd, up_bound, down_bound))
+    assert max(eu, nu) <= up_bound and max(ed, nd) <= down_bound, (eu, nu, up_bound, ed, nd, down_bound)

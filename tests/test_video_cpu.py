@@ -11,6 +11,7 @@ import sys
 import numpy as np
 import pytest
 
+import yuv_float_ref as F
 import yuv_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -18,6 +19,8 @@ PKG = os.path.join(ROOT, "fldr-vfi_amd")
 INC = os.path.join(ROOT, "include")
 HDR = os.path.join(INC, "fldr_video.h")
 LIB = os.path.join(PKG, "libfldr_video.so")
+TEST_LIB = os.path.join(PKG, "libfldr_video_test.so")                          # -DFLDR_TEST_HOOKS: + include/fldr_video_test_hooks.h
+HOOKS_HDR = os.path.join(INC, "fldr_video_test_hooks.h")
 COLOR_H = os.path.join(PKG, "video", "yuv_color.h")
 
 
@@ -84,19 +87,17 @@ def test_example_builds_with_cc(tmp_path):
     assert u.returncode == 2 and "usage" in u.stderr
 
 
-def test_no_unsafe_packed_fp32_in_the_video_library():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_pk_opsel.py"), LIB], capture_output=True, text=True)
+def _no_unsafe_packed_fp32(lib):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_pk_opsel.py"), lib], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
 
 
-def test_no_ashr_pk_in_the_video_library():
-    """v_ashr_pk_u8_i32 / v_ashr_pk_i8_i32 leave bits 16..31 of their result stale on gfx950, while hipcc ORs that result with other
-    bytes (video_kernels.hip, pack4): none may be in the library."""
+def _no_ashr_pk(lib):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import tempfile
     import kernel_resources as KR
     n = 0
-    for blob in KR.code_objects(LIB):
+    for blob in KR.code_objects(lib):
         with tempfile.NamedTemporaryFile(suffix=".co") as f:
             f.write(blob)
             f.flush()
@@ -104,6 +105,81 @@ def test_no_ashr_pk_in_the_video_library():
         assert "yuv420_to_planar_pair_kernel" in txt
         n += len(re.findall(r"\bv_ashr_pk_[ui]8_i32\b", txt))
     assert n == 0
+
+
+def test_no_unsafe_packed_fp32_in_the_video_library():
+    _no_unsafe_packed_fp32(LIB)
+
+
+def test_no_ashr_pk_in_the_video_library():
+    """v_ashr_pk_u8_i32 / v_ashr_pk_i8_i32 leave bits 16..31 of their result stale on gfx950, while hipcc ORs that result with other
+    bytes (video_kernels.hip, pack4): none may be in the library."""
+    _no_ashr_pk(LIB)
+
+
+# ---- the test build: libfldr_video_test.so, the binary tests/test_gpu_video_convert.py executes ------------------------------------------
+def test_test_library_exports_exactly_the_header_and_the_hooks():
+    declared = _declared(HDR, "FLDR_VIDEO_API")
+    hooks = _declared(HOOKS_HDR, "FLDR_VIDEO_API")
+    assert hooks == {"fldr_video_debug_to_planar", "fldr_video_debug_from_planar", "fldr_video_debug_last_path"}
+    assert _syms(TEST_LIB, ["--defined-only"]) == declared | hooks
+    import fldr_video
+    assert set(fldr_video.HOOKS) == hooks and not set(fldr_video.HOOKS) & set(fldr_video.EXPORTS)
+
+
+def test_product_library_has_no_hook():
+    names = _syms(LIB, []) | _syms(os.path.join(PKG, "libfldr_model.so"), [])
+    assert not [n for n in names if "debug" in n.lower()], sorted(names)
+    assert "debug" not in open(HDR).read().lower()
+
+
+def test_test_library_links_like_the_product():
+    dyn = subprocess.run(["readelf", "-d", TEST_LIB], capture_output=True, text=True, check=True).stdout
+    assert re.search(r"NEEDED.*\[libfldr_model\.so\]", dyn) and not re.search(r"NEEDED.*\[libfldr_(hip|video)\.so\]", dyn), dyn
+    assert re.search(r"R(UN)?PATH.*\$ORIGIN", dyn), dyn
+    assert _syms(TEST_LIB, ["--undefined-only"]) == _syms(LIB, ["--undefined-only"])       # the hooks call nothing the product does not
+
+
+@pytest.mark.parametrize("compiler", [["gcc", "-std=c99", "-x", "c"], ["g++", "-std=c++11", "-x", "c++"]])
+def test_hooks_header_is_plain_c99_and_cxx(compiler, tmp_path):
+    if not shutil.which(compiler[0]):
+        pytest.skip(compiler[0] + " not installed")
+    src = tmp_path / "h.c"
+    src.write_text('#include "fldr_video_test_hooks.h"\n'
+                   'int main(void) { fldr_video_frame in[2]; fldr_video_format f; fldr_video_frame o;\n'
+                   '  return fldr_video_debug_to_planar(in, &f, 0, 2, 2, 0) + fldr_video_debug_from_planar(0, &o, &f, 2, 2, 0) + fldr_video_debug_last_path(); }\n')
+    r = subprocess.run(compiler + ["-Wall", "-Wextra", "-Werror", "-pedantic", "-Wno-uninitialized", "-fsyntax-only", "-I" + INC, str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+
+
+def test_no_unsafe_packed_fp32_in_the_video_test_library():
+    _no_unsafe_packed_fp32(TEST_LIB)
+
+
+def test_no_ashr_pk_in_the_video_test_library():
+    _no_ashr_pk(TEST_LIB)
+
+
+def test_hook_sources_stay_out_of_the_product_build():
+    """Everything the test build adds sits behind FLDR_TEST_HOOKS: with the macro undefined the preprocessor drops every line that names
+    a hook, so libfldr_video.so is compiled from the text it was compiled from before the hooks existed."""
+    for name in ("video_host.hip", "video_kernels.hip", "video_internal.h"):
+        depth, live = [], []
+        for line in open(os.path.join(PKG, "video", name)).read().splitlines():
+            t = line.strip()
+            if t.startswith("#ifdef FLDR_TEST_HOOKS"):
+                depth.append("hooks")
+            elif t.startswith(("#if", "#ifdef", "#ifndef")):
+                depth.append("other")
+            elif t.startswith("#else") and depth and depth[-1] == "hooks":
+                depth[-1] = "other"
+            elif t.startswith("#endif"):
+                depth.pop()
+            elif "hooks" not in depth:
+                live.append(t)
+        text = "\n".join(l for l in live if not l.startswith("//"))
+        assert "g_last_path" not in text and "fldr_video_debug" not in text and "test_hooks.h" not in text, name
 
 
 def test_binding_struct_sizes_and_version():
@@ -307,3 +383,89 @@ def test_session_argument_errors_before_any_device_call():
     assert l.fldr_video_session_push(None, None, None, ctypes.byref(n)) == V.E_ARG
     assert l.fldr_video_session_reset(None) == V.E_ARG
     l.fldr_video_session_destroy(None)
+
+
+@pytest.mark.parametrize("layout", ["nv12", "i420"])
+@pytest.mark.parametrize("depth", [8, 10])
+def test_hook_argument_errors_before_any_device_call(layout, depth):
+    """The converter hooks of libfldr_video_test.so validate as fldr_video_forward does (format, frame, H, W >= 2) and want the planar
+    side 256-byte aligned; every refusal comes back before a device call, so this runs without a GPU."""
+    import fldr_video as V
+    l = V.test_hooks()
+    assert l.fldr_video_debug_last_path() == -1                                # nothing launched in this process
+    H, W, b = 64, 64, depth // 8 if depth == 8 else 2
+    buf = np.zeros(H * W * 16 + 512, np.uint8)
+    base = (buf.ctypes.data + 255) // 256 * 256
+    shapes = V.plane_shapes(layout, H, W)
+
+    def frame():
+        f = V.Frame()
+        for p, (r, c) in enumerate(shapes):
+            f.plane[p], f.pitch[p] = base, c * b
+        return f
+
+    def call(mutate=lambda fr, fmt: None, planar=base, H=H, W=W, which="both"):
+        codes = []
+        fmt = V.Format(layout, depth=depth)
+        frames = (V.Frame * 2)(frame(), frame())
+        mutate(frames[1], fmt)
+        if which in ("both", "in"):
+            codes.append(l.fldr_video_debug_to_planar(frames, ctypes.byref(fmt), planar, H, W, None))
+        if which in ("both", "out"):
+            codes.append(l.fldr_video_debug_from_planar(planar, ctypes.byref(frames[1]), ctypes.byref(fmt), H, W, None))
+        assert len(set(codes)) == 1, codes
+        return codes[0]
+    assert call(planar=None) == V.E_ARG
+    assert call(planar=base + 128) == V.E_ARG and call(planar=base + 8) == V.E_ARG          # the workspace's alignment: 256 bytes
+    assert call(H=1) == V.E_ARG and call(W=1) == V.E_ARG
+    assert l.fldr_video_debug_to_planar(None, ctypes.byref(V.Format(layout)), base, H, W, None) == V.E_ARG
+    assert l.fldr_video_debug_from_planar(base, None, ctypes.byref(V.Format(layout)), H, W, None) == V.E_ARG
+    assert l.fldr_video_debug_to_planar((V.Frame * 2)(frame(), frame()), None, base, H, W, None) == V.E_ARG
+    for field, val in (("layout", 2), ("matrix", 2), ("range", -1), ("depth", 9), ("depth", 12)):
+        assert call(lambda fr, fmt: setattr(fmt, field, val)) == V.E_FORMAT, field
+    assert call(lambda fr, fmt: fmt.reserved.__setitem__(3, 1)) == V.E_FORMAT
+    for p in range(len(shapes)):
+        assert call(lambda fr, fmt: fr.plane.__setitem__(p, None)) == V.E_PLANE, p
+        assert call(lambda fr, fmt: fr.pitch.__setitem__(p, shapes[p][1] * b - b)) == V.E_PITCH, p
+        if depth == 10:
+            assert call(lambda fr, fmt: fr.plane.__setitem__(p, base + 1)) == V.E_PLANE, p
+            assert call(lambda fr, fmt: fr.pitch.__setitem__(p, shapes[p][1] * b + 1)) == V.E_PITCH, p
+    assert l.fldr_video_debug_last_path() == -1                                # and still nothing was launched
+
+
+# ---- the integer definition against the standard in float64 (tests/yuv_float_ref.py) ------------------------------------------------------
+@pytest.mark.parametrize("mat", list(O.MATRICES))
+@pytest.mark.parametrize("rng", O.RANGES)
+def test_all_triples_are_within_half_a_code_of_the_float_definition(mat, rng):
+    """Every 8-bit (Y, U, V) and (R, G, B) triple through the integer 4:4:4 forms against the clipped float64 value of the definition
+    written from the standard: 0.5 for the rounding plus the quantisation of the 16-bit coefficients.  Bound 0.51; measured maximum over the
+    four formats 0.5016 (to RGB: BT.601 limited) and 0.5020 (to YUV: BT.709 limited)."""
+    v = np.arange(256, dtype=np.int64)
+    A, B_, C = (a.ravel() for a in np.meshgrid(v, v, v, indexing="ij"))
+    worst = {}
+    for name, got, ref in (("to RGB", O.yuv444_to_rgb(A, B_, C, mat, rng), F.ycbcr_to_rgb(A, B_, C, mat, rng)),
+                           ("to YUV", O.rgb_to_yuv444(A, B_, C, mat, rng), F.rgb_to_ycbcr(A, B_, C, mat, rng))):
+        worst[name] = max(float(np.abs(g - F.clip(r)).max()) for g, r in zip(got, ref))
+    print("8-bit 4:4:4, %s %s: max |integer - float| = %.4f (to RGB), %.4f (to YUV)" % (mat, rng, worst["to RGB"], worst["to YUV"]))
+    assert max(worst.values()) <= 0.51, worst
+
+
+@pytest.mark.parametrize("mat", list(O.MATRICES))
+@pytest.mark.parametrize("rng", O.RANGES)
+def test_noise_frames_are_within_the_derived_bound_of_the_float_definition(mat, rng):
+    """Full 4:2:0 noise frames (odd and even sizes) in both directions, depth 8: the integer oracle against the float64 definition with its
+    own statement of the siting and the filters.  The bound is derived from the table: 0.5 + sum over the expression's coefficients of
+    2^-17 x the largest |operand| (yuv_float_ref.coefficient_bound): 0.5039 to RGB, 0.5058 to YUV.  Measured maxima over the four formats: 0.5013 to RGB, 0.5010 to YUV."""
+    k = O.constants(mat, rng)
+    up_bound, down_bound = 0.5 + F.coefficient_bound(k, 8, "to_rgb"), 0.5 + F.coefficient_bound(k, 8, "to_yuv")
+    assert 0.5 < up_bound < 0.504 and 0.5 < down_bound < 0.506
+    eu = ed = 0.0
+    for H, W in ((203, 301), (64, 96), (2, 2), (3, 5)):
+        g = np.random.default_rng(H * W)
+        ch, cw = O.chroma_size(H, W)
+        Y, U, V = (g.integers(0, 256, s).astype(np.uint8) for s in ((H, W), (ch, cw), (ch, cw)))
+        eu = max(eu, float(np.abs(O.yuv420_to_bgr(Y, U, V, mat, rng) - F.yuv420_to_bgr(Y, U, V, mat, rng)).max()))
+        bgr = g.integers(0, 256, (3, H, W)).astype(np.uint8)
+        ed = max(ed, max(float(np.abs(i - f).max()) for i, f in zip(O.bgr_to_yuv420(bgr, mat, rng), F.bgr_to_yuv420(bgr, mat, rng))))
+    print("8-bit 4:2:0 noise, %s %s: max |integer - float| = %.4f (to RGB, bound %.4f), %.4f (to YUV, bound %.4f)" % (mat, rng, eu, up_bound, ed, down_bound))
+    assert eu <= up_bound and ed <= down_bound, (eu, up_bound, ed, down_bound)
