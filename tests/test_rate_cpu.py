@@ -1,0 +1,382 @@
+"""CPU checks of the rate API (include/fldr_rate.h, libfldr_rate.so): the cut measure's definition (tests/scene_oracle.py) on the
+repository's own content under the header's default thresholds, the schedule of the rate converter in exact rationals, the library's
+symbol table and link, the header as plain C99 / C++, the C example, the code-generation guards, the binding's struct mirrors, and the
+argument checks — which happen before any device call, so they run without a GPU."""
+import ctypes
+import os
+import re
+import shutil
+import subprocess
+import sys
+from fractions import Fraction
+
+import numpy as np
+import pytest
+
+import content_pairs as CP
+import rate_frames as RF
+import scene_oracle as S
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, "fldr-vfi_amd")
+INC = os.path.join(ROOT, "include")
+HDR = os.path.join(INC, "fldr_rate.h")
+LIB = os.path.join(PKG, "libfldr_rate.so")
+
+
+def _declared(path, macro):
+    return set(re.findall(macro + r"\s+[^;(]*?\b(fldr_[a-z0-9_]+)\s*\(", open(path).read()))
+
+
+def _syms(lib, args):
+    out = subprocess.run(["nm", "-D"] + args + [lib], capture_output=True, text=True, check=True).stdout
+    return set(l.split()[-1] for l in out.splitlines() if l.strip())
+
+
+# ---- the cut measure on the repository's content ----------------------------------------------------------------------------------------
+def test_defaults_are_parsed_from_the_header():
+    import fldr_rate as R
+    assert S.defaults() == (R.SCENE_SAD_DEFAULT, R.SCENE_HIST_DEFAULT)
+    assert all(1 <= v <= 1000 for v in S.defaults())
+
+
+def test_oracle_on_hand_worked_frames():
+    a = np.array([[0, 10, 255], [7, 7, 7]], np.uint8)
+    b = np.array([[5, 10, 0], [7, 8, 9]], np.uint8)
+    m = S.measure((a,), (b,), ("nv12", 8), (1, 1))
+    assert m["sad"] == 5 + 0 + 255 + 0 + 1 + 2
+    # h0: 0, 10, 255, 7 x 3; h1: 5, 10, 0, 7, 8, 9 -> bins 255, 5, 8, 9: 1 each, bin 7: 2
+    assert m["hist_dist"] == 6 and m["cut"] == 1
+    # depth 10: P010 reads word >> 8, yuv420p10le (word & 0x3ff) >> 2; the other bits are ignored
+    w = np.array([[0x1234, 0xffff]], np.uint16)
+    assert S.y8(w, "nv12", 10).tolist() == [[0x12, 0xff]] and S.y8(w, "i420", 10).tolist() == [[(0x234 >> 2), 0xff]]
+    black, white = np.zeros((4, 6), np.uint8), np.full((4, 6), 255, np.uint8)
+    m = S.measure((black,), (white,), ("i420", 8))
+    assert m == {"sad": 255 * 24, "hist_dist": 48, "cut": 1}
+    assert S.measure((black,), (black,), ("i420", 8)) == {"sad": 0, "hist_dist": 0, "cut": 0}
+    # both clauses are needed: each threshold alone at its maximum keeps a black / white pair from being a cut only when it is missed
+    assert S.measure((black,), (white,), ("i420", 8), (1000, 1000))["cut"] == 1
+    grey = np.full((4, 6), 254, np.uint8)
+    assert S.measure((black,), (grey,), ("i420", 8), (1000, 1))["cut"] == 0 and S.measure((black,), (grey,), ("i420", 8), (996, 1000))["cut"] == 1
+
+
+TABLE_SIZES = [(1080, 1920, (0,)), (270, 480, (0, 1, 2))]
+
+
+@pytest.mark.parametrize("depth", [8, 10])
+@pytest.mark.parametrize("H,W,seeds", TABLE_SIZES)
+@pytest.mark.parametrize("case", list(CP.CASES))
+def test_default_thresholds_classify_the_content_pairs(case, H, W, seeds, depth):
+    """Every case of tests/content_pairs.py, BT.709 limited: cut, fade and fade_in are cuts under the header's defaults, nothing else is.
+    The figures (sad, hist_dist in permille of 255 H W and 2 H W) are printed; INTEGRATION.md carries the table."""
+    for seed in seeds:
+        a, b = RF.content(case, H, W, seed, "i420", depth)
+        m = S.measure(a, b, ("i420", depth))
+        print("%s %dx%d seed %d depth %d: sad %d, hist %d permille, cut %d" % ((case, H, W, seed, depth) + S.permille(m, H, W) + (m["cut"],)))
+        assert m["cut"] == (1 if case in RF.CUT_CASES else 0), (case, seed, S.permille(m, H, W))
+
+
+def test_nv12_and_i420_measure_the_same():
+    for depth in (8, 10):
+        a, b = RF.content("cut", 270, 480, 0, "i420", depth)
+        c, d = RF.content("cut", 270, 480, 0, "nv12", depth)
+        assert S.measure(a, b, ("i420", depth)) == S.measure(c, d, ("nv12", depth))
+
+
+# ---- the schedule ----------------------------------------------------------------------------------------------------------------------
+RATES = [(24, 60), (25, 60), ((24000, 1001), 120), (30, 30), (60, 24)]
+
+
+@pytest.mark.parametrize("in_rate,out_rate", RATES)
+def test_schedule_is_the_rational_rule(in_rate, out_rate):
+    import fldr_rate as R
+    N = 1000
+    A, B = R.ratio(in_rate, out_rate)
+    q = Fraction(*in_rate) / Fraction(out_rate) if isinstance(in_rate, tuple) else Fraction(in_rate, out_rate)
+    assert Fraction(A, B) == q and np.gcd(A, B) == 1
+    sched = R.schedule(N, in_rate, out_rate)
+    assert len(sched) == N + 1 and sched[0] == []
+    outs = [o for push in sched for o in push]
+    assert len(outs) == ((N - 1) * B) // A + 1
+    assert [o[0] for o in outs] == list(range(len(outs)))
+    mo = R.max_out(in_rate, out_rate)
+    assert mo == -(-B // A)
+    prev = Fraction(-1)
+    for n, push in enumerate(sched):
+        assert len(push) <= mo
+        for j, i, r, b in push:
+            pos = j * q                                             # exact
+            assert b == B and i == pos.numerator // pos.denominator and Fraction(r, B) == pos - i and 0 <= r < B
+            assert (r == 0) == ((j * A) % B == 0)
+            assert pos >= prev
+            prev = pos
+            if n < N:
+                assert n >= 1 and n - 1 <= pos < n and i == n - 1
+            else:
+                assert pos == N - 1 and r == 0                     # the flush: exactly the last frame
+    assert max(len(p) for p in sched) == mo
+    if A == B:
+        assert all(len(p) == 1 and p[0][2] == 0 for p in sched[1:])
+    # nothing is lost at the end: the next output would lie behind the last frame
+    assert len(outs) * q > N - 1
+
+
+def test_schedule_small_cases():
+    import fldr_rate as R
+    assert R.schedule(0, 24, 60) == [[]]
+    assert R.schedule(1, 24, 60) == [[], [(0, 0, 0, 5)]]
+    s = R.schedule(3, 24, 60)                                       # A / B = 2 / 5
+    assert s == [[], [(0, 0, 0, 5), (1, 0, 2, 5), (2, 0, 4, 5)], [(3, 1, 1, 5), (4, 1, 3, 5)], [(5, 2, 0, 5)]]
+    s = R.schedule(6, 60, 24)                                       # A / B = 5 / 2: frames 0, 2.5, 5
+    assert s == [[], [(0, 0, 0, 2)], [], [(1, 2, 1, 2)], [], [], [(2, 5, 0, 2)]]
+
+
+# ---- the library ------------------------------------------------------------------------------------------------------------------------
+def test_library_exports_exactly_the_header():
+    declared = _declared(HDR, "FLDR_RATE_API")
+    assert len(declared) == 12, sorted(declared)
+    assert _syms(LIB, ["--defined-only"]) == declared
+    import fldr_rate
+    assert set(fldr_rate.EXPORTS) == declared
+
+
+def test_library_links_only_the_video_and_model_apis():
+    dyn = subprocess.run(["readelf", "-d", LIB], capture_output=True, text=True, check=True).stdout
+    assert re.search(r"NEEDED.*\[libfldr_video\.so\]", dyn), dyn
+    assert not re.search(r"NEEDED.*\[libfldr_hip\.so\]", dyn), dyn
+    assert re.search(r"R(UN)?PATH.*\$ORIGIN", dyn), dyn
+    used = set(n for n in _syms(LIB, ["--undefined-only"]) if n.startswith("fldr_"))
+    allowed = _declared(os.path.join(INC, "fldr_video.h"), "FLDR_VIDEO_API") | _declared(os.path.join(INC, "fldr_model.h"), "FLDR_MODEL_API")
+    assert used and used <= allowed, sorted(used)
+    assert "fldr_video_forward" in used
+
+
+def test_the_other_headers_and_libraries_know_nothing_of_the_rate_api():
+    for name in ("fldr_hip.h", "fldr_model.h", "fldr_video.h", "fldr_video_test_hooks.h", "fldr_hip_test_hooks.h"):
+        text = open(os.path.join(INC, name)).read()
+        assert "fldr_rate" not in text and "fldr_scene" not in text, name
+    for name in ("libfldr_hip.so", "libfldr_model.so", "libfldr_video.so"):
+        assert not [n for n in _syms(os.path.join(PKG, name), []) if "fldr_rate" in n or "fldr_scene" in n], name
+
+
+@pytest.mark.parametrize("compiler", [["gcc", "-std=c99", "-x", "c"], ["g++", "-std=c++11", "-x", "c++"]])
+def test_header_is_plain_c99_and_cxx(compiler, tmp_path):
+    if not shutil.which(compiler[0]):
+        pytest.skip(compiler[0] + " not installed")
+    src = tmp_path / "h.c"
+    src.write_text('#include "fldr_rate.h"\nint main(void) { return fldr_rate_sizeof(0) > 0 && FLDR_SCENE_STATE_BYTES == 4096 ? 0 : 1; }\n')
+    r = subprocess.run(compiler + ["-Wall", "-Wextra", "-Werror", "-pedantic", "-fsyntax-only", "-I" + INC, str(src)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert "hip/" not in open(HDR).read()
+
+
+def test_example_builds_with_cc(tmp_path):
+    cc = shutil.which("cc") or shutil.which("gcc")
+    if not cc:
+        pytest.skip("no C compiler")
+    exe = tmp_path / "fldr_fps"
+    r = subprocess.run([cc, "-std=c99", "-Wall", "-Wextra", "-Werror", "-pedantic", "-I" + INC, "-o", str(exe),
+                        os.path.join(ROOT, "examples", "fldr_fps.c"), "-L" + PKG, "-l:libfldr_rate.so", "-l:libfldr_video.so", "-l:libfldr_model.so",
+                        "-Wl,-rpath," + PKG], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    src = open(os.path.join(ROOT, "examples", "fldr_fps.c")).read()
+    assert "hip" not in re.sub(r"/\*.*?\*/", "", src, flags=re.S).lower()
+    u = subprocess.run([str(exe)], capture_output=True, text=True)            # no arguments: usage, no device touched
+    assert u.returncode == 2 and "usage" in u.stderr
+    u = subprocess.run([str(exe), "w.npz", "64", "64", "24/0", "60"], capture_output=True, text=True)     # a bad rate: usage too
+    assert u.returncode == 2 and "usage" in u.stderr
+
+
+def test_no_unsafe_packed_fp32_in_the_rate_library():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_pk_opsel.py"), LIB], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
+def _disassembly():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import tempfile
+    import kernel_resources as KR
+    out = []
+    for blob in KR.code_objects(LIB):
+        with tempfile.NamedTemporaryFile(suffix=".co") as f:
+            f.write(blob)
+            f.flush()
+            out.append(subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", f.name], capture_output=True, text=True, check=True).stdout)
+    return "\n".join(out)
+
+
+def test_kernels_use_the_sad_instructions_and_no_ashr_pk():
+    txt = _disassembly()
+    assert "scene_accumulate_kernel" in txt and "select_on_cut_kernel" in txt
+    assert len(re.findall(r"\bv_ashr_pk_[ui]8_i32\b", txt)) == 0
+    assert re.search(r"\bv_sad_u8\b", txt) and re.search(r"\bv_sad_u16\b", txt)
+    assert re.search(r"\bds_add_u32\b", txt)                                   # the histograms live in LDS
+    assert not re.search(r"\bs_(buffer_|scratch_)?(store|atomic)_", txt)      # vector stores only
+
+
+def test_kernels_use_no_scratch():
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import kernel_resources as KR
+    ks = KR.kernels(LIB)
+    assert len(ks) == 9, [k["name"] for k in ks]          # zero, decide, select, accumulate x (3 sample forms x wide / per-sample)
+    for k in ks:
+        assert k.get("scratch", -1) == 0 and k.get("vgpr_spills", -1) == 0 and k.get("sgpr_spills", -1) == 0, k
+
+
+def test_binding_struct_sizes_and_version():
+    import fldr_rate as R
+    l = R.lib()
+    text = open(HDR).read()
+    assert l.fldr_rate_version() == R.RATE_VERSION == int(re.search(r"#define FLDR_RATE_VERSION (\d+)", text).group(1)) == 100
+    for which, cls in enumerate((R.SceneParams, R.SceneResult, R.RateConfig)):
+        assert l.fldr_rate_sizeof(which) == ctypes.sizeof(cls)
+    assert ctypes.sizeof(R.SceneResult) == 32 and ctypes.sizeof(R.SceneParams) == 16
+    assert l.fldr_rate_sizeof(3) == R.E_ARG
+    for name, v in (("E_ARG", R.E_ARG), ("E_FORMAT", R.E_FORMAT), ("E_STATE", R.E_STATE), ("E_RATIO", R.E_RATIO), ("E_DEVICE", R.E_DEVICE)):
+        assert re.search(r"#define FLDR_RATE_%s\s+\((-?\d+)\)" % name, text).group(1) == str(v)
+        assert v <= -200                                                       # apart from the video and model ranges
+        assert l.fldr_rate_error_string(v).decode().startswith("fldr_rate")
+    assert int(re.search(r"#define FLDR_SCENE_STATE_BYTES\s+(\d+)", text).group(1)) == R.SCENE_STATE_BYTES
+    assert int(re.search(r"#define FLDR_RATE_MAX_OUT\s+(\d+)", text).group(1)) == R.MAX_OUT == 64
+    assert l.fldr_rate_error_string(-101).decode().startswith("fldr_video")   # video codes pass through
+    assert l.fldr_rate_error_string(-3).decode().startswith("fldr_model")     # and model codes through it
+
+
+# ---- argument errors without a device ---------------------------------------------------------------------------------------------------
+def _frames(V, layout, depth, H=64, W=64):
+    buf = np.zeros(H * W * 8 + 512, np.uint8)
+    base = (buf.ctypes.data + 255) // 256 * 256
+    b = 2 if depth == 10 else 1
+    fr = []
+    for _ in range(2):
+        f = V.Frame()
+        for p, (r, c) in enumerate(V.plane_shapes(layout, H, W)):
+            f.plane[p], f.pitch[p] = base, c * b
+        fr.append(f)
+    return buf, base, fr
+
+
+@pytest.mark.parametrize("layout", ["nv12", "i420"])
+@pytest.mark.parametrize("depth", [8, 10])
+def test_measure_argument_errors_before_any_device_call(layout, depth):
+    import fldr_rate as R
+    import fldr_video as V
+    H = W = 64
+    b = 2 if depth == 10 else 1
+    buf, base, _ = _frames(V, layout, depth)
+    shapes = V.plane_shapes(layout, H, W)
+
+    def call(mutate=lambda fr, fmt: None, params=None, state=base, H=H, W=W):
+        _, _, fr = _frames(V, layout, depth)
+        for f in fr:
+            for p in range(len(shapes)):
+                f.plane[p] = base
+        fmt = V.Format(layout, depth=depth)
+        mutate(fr[1], fmt)
+        return R.scene_measure_raw(H, W, fmt, fr, params, state, None)
+    assert call(state=None) == R.E_STATE
+    assert call(state=base + 128) == R.E_STATE and call(state=base + 16) == R.E_STATE
+    assert call(H=0) == R.E_ARG and call(W=0) == R.E_ARG and call(H=-1) == R.E_ARG
+    assert R.scene_measure_raw(H, W, None, _frames(V, layout, depth)[2], None, base, None) == R.E_ARG
+    assert R.scene_measure_raw(H, W, V.Format(layout, depth=depth), None, None, base, None) == R.E_ARG
+    for bad in ((-1, 0), (0, -1), (1001, 0), (0, 1001)):
+        assert call(params=R.SceneParams(*bad)) == R.E_ARG, bad
+    p = R.SceneParams()
+    p.reserved[1] = 1
+    assert call(params=p) == R.E_ARG
+    for field, val in (("layout", 2), ("matrix", 2), ("range", -1), ("depth", 9), ("depth", 12)):
+        assert call(lambda fr, fmt: setattr(fmt, field, val)) == V.E_FORMAT, field
+    assert call(lambda fr, fmt: fmt.reserved.__setitem__(3, 1)) == V.E_FORMAT
+    for q in range(len(shapes)):
+        assert call(lambda fr, fmt: fr.plane.__setitem__(q, None)) == V.E_PLANE, q
+        assert call(lambda fr, fmt: fr.pitch.__setitem__(q, shapes[q][1] * b - b)) == V.E_PITCH, q
+        if depth == 10:
+            assert call(lambda fr, fmt: fr.plane.__setitem__(q, base + 1)) == V.E_PLANE, q
+            assert call(lambda fr, fmt: fr.pitch.__setitem__(q, shapes[q][1] * b + 1)) == V.E_PITCH, q
+    assert not buf.any()
+
+
+def _io(V, H=64, W=64, layout="nv12", n_t=1):
+    buf = np.zeros(H * W * 4, np.uint8)
+    io = V.IO()
+    io.H, io.W = H, W
+    io.in_format, io.out_format = V.Format(layout), V.Format(layout)
+    shapes = V.plane_shapes(layout, H, W)
+    for f in range(2):
+        for p, (r, c) in enumerate(shapes):
+            io.in_[f].plane[p], io.in_[f].pitch[p] = buf.ctypes.data, c
+    outs = (V.Frame * n_t)()
+    for k in range(n_t):
+        for p, (r, c) in enumerate(shapes):
+            outs[k].plane[p], outs[k].pitch[p] = buf.ctypes.data, c
+    io.n_t, io.t, io.out = n_t, buf.ctypes.data, ctypes.cast(outs, ctypes.POINTER(V.Frame))
+    io._keep = (buf, outs)
+    return io
+
+
+@pytest.mark.parametrize("layout", ["nv12", "i420"])
+def test_forward_argument_errors_before_any_device_call(layout):
+    import fldr_rate as R
+    import fldr_video as V
+    l = R.lib()
+    call = lambda io, p=None: l.fldr_rate_forward(None, ctypes.byref(io), ctypes.byref(p) if p is not None else None, None, 0, None)
+    assert call(_io(V, layout=layout)) == V.E_ARG                           # valid io, no model: the video library's refusal
+    assert l.fldr_rate_forward(None, None, None, None, 0, None) == R.E_ARG
+    cases = []
+    for field, val in (("layout", 1 - V.LAYOUTS[layout]), ("matrix", 0), ("range", 1), ("depth", 10)):
+        io = _io(V, layout=layout); setattr(io.out_format, field, val); cases.append((io, R.E_FORMAT))     # valid, but not the input's
+    io = _io(V, layout=layout); io.in_format.depth = 0; cases.append((io, V.E_ARG))                         # 0 and 8 are one depth
+    for field, val in (("layout", 2), ("matrix", 2), ("range", 2)):
+        io = _io(V, layout=layout); setattr(io.in_format, field, val); setattr(io.out_format, field, val); cases.append((io, V.E_FORMAT))
+    io = _io(V, layout=layout); io.in_[0].pitch[0] = 63; cases.append((io, V.E_PITCH))
+    io = _io(V, layout=layout, n_t=2); io.out[1].pitch[1] = (32 if layout == "i420" else 64) - 1; cases.append((io, V.E_PITCH))
+    io = _io(V, layout=layout); io.in_[1].plane[1] = None; cases.append((io, V.E_PLANE))
+    io = _io(V, layout=layout); io.out[0].plane[0] = None; cases.append((io, V.E_PLANE))
+    io = _io(V, layout=layout); io.n_t = 0; cases.append((io, V.E_ARG))
+    io = _io(V, layout=layout); io.t = None; cases.append((io, V.E_ARG))
+    io = _io(V, layout=layout); io.W = 1; cases.append((io, V.E_ARG))
+    for io, code in cases:
+        assert call(io) == code
+    assert call(_io(V, layout=layout), R.SceneParams(1001, 0)) == R.E_ARG
+    assert call(_io(V, layout=layout), R.SceneParams(0, -5)) == R.E_ARG
+    assert l.fldr_rate_workspace_bytes(None, 64, 64, 1) == V.E_ARG
+
+
+def test_converter_argument_errors_before_any_device_call():
+    import fldr_rate as R
+    import fldr_video as V
+    l = R.lib()
+    h = ctypes.c_void_p()
+
+    def create(**kw):
+        cfg = R.RateConfig()
+        cfg.H, cfg.W, cfg.format = 64, 64, V.Format("i420")
+        cfg.in_num, cfg.in_den, cfg.out_num, cfg.out_den, cfg.scene = 24, 1, 60, 1, 1
+        for k, v in kw.items():
+            if k == "mutate":
+                v(cfg)
+            else:
+                setattr(cfg, k, v)
+        return l.fldr_rate_create(None, ctypes.byref(cfg), ctypes.byref(h))
+    assert create() == R.E_ARG                                               # valid, no model
+    for term in ("in_num", "in_den", "out_num", "out_den"):
+        assert create(**{term: 0}) == R.E_RATIO and create(**{term: -24}) == R.E_RATIO, term
+    assert create(in_num=1, out_num=64) == R.E_ARG                           # max_out = 64: allowed (and then no model)
+    assert create(in_num=1, out_num=65) == R.E_RATIO                         # max_out = 65
+    assert create(in_num=2, out_num=129) == R.E_RATIO                        # ceil(129 / 2) = 65
+    assert create(in_num=2, in_den=1, out_num=127, out_den=1) == R.E_ARG     # ceil(127 / 2) = 64
+    assert create(in_num=2 ** 25 + 1, out_num=2 ** 25) == R.E_RATIO          # reduced terms above 2^24: t = r / B would not be exact
+    assert create(in_num=24000, in_den=1001, out_num=120) == R.E_ARG
+    assert create(scene=2) == R.E_ARG and create(scene=-1) == R.E_ARG
+    assert create(H=1) == R.E_ARG and create(device=-1) == R.E_ARG
+    assert create(mutate=lambda c: c.reserved.__setitem__(2, 1)) == R.E_ARG
+    assert create(mutate=lambda c: setattr(c.scene_params, "sad_permille", 1001)) == R.E_ARG
+    assert create(mutate=lambda c: setattr(c.format, "layout", 3)) == V.E_FORMAT
+    assert l.fldr_rate_create(None, None, ctypes.byref(h)) == R.E_ARG
+    n = ctypes.c_int()
+    assert l.fldr_rate_push(None, None, None, ctypes.byref(n), None) == R.E_ARG
+    assert l.fldr_rate_flush(None, None, ctypes.byref(n)) == R.E_ARG
+    assert l.fldr_rate_reset(None) == R.E_ARG
+    assert l.fldr_rate_max_out(None) == R.E_ARG
+    l.fldr_rate_destroy(None)
