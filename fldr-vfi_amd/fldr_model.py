@@ -67,23 +67,29 @@ class ModelError(RuntimeError):
         self.code = code
 
 
+def load_library(path, signatures, structs, prefix, version):
+    """ctypes.CDLL(path) with `signatures` set, checked against a binding: sizeof(structs[i]) == <prefix>_sizeof(i) and <prefix>_version()
+    == version.  ImportError when the file has not been built or does not match.  fldr_video and fldr_rate load through it too."""
+    if not os.path.exists(path):
+        raise ImportError("%s is missing — build it with `make -C fldr-vfi_amd/csrc` (or __graft_entry__.build())" % path)
+    l = ctypes.CDLL(path)
+    for name, (res, args) in signatures.items():
+        fn = getattr(l, name)
+        fn.restype, fn.argtypes = res, args
+    sizeof, reported = getattr(l, prefix + "_sizeof"), getattr(l, prefix + "_version")()
+    for which, cls in enumerate(structs):
+        if sizeof(which) != ctypes.sizeof(cls):
+            raise ImportError("%s: sizeof(%s) is %d in the library, %d in this binding" % (path, cls.__name__, sizeof(which), ctypes.sizeof(cls)))
+    if reported != version:
+        raise ImportError("%s reports version %d, this binding is written for %d: rebuild it" % (path, reported, version))
+    return l
+
+
 def lib():
     """The loaded libfldr_model.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError("%s is missing — build it with `make -C fldr-vfi_amd/csrc` (or __graft_entry__.build())" % LIB_PATH)
-        l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = res, args
-        for which, cls in enumerate((Tensor, Config, IO)):
-            if l.fldr_model_sizeof(which) != ctypes.sizeof(cls):
-                raise ImportError("%s: sizeof(%s) is %d in the library, %d in this binding" % (LIB_PATH, cls.__name__, l.fldr_model_sizeof(which),
-                                                                                              ctypes.sizeof(cls)))
-        if l.fldr_model_version() != MODEL_VERSION:
-            raise ImportError("%s reports version %d, this binding is written for %d: rebuild it" % (LIB_PATH, l.fldr_model_version(), MODEL_VERSION))
-        _lib = l
+        _lib = load_library(LIB_PATH, _SIGNATURES, (Tensor, Config, IO), "fldr_model", MODEL_VERSION)
     return _lib
 
 

@@ -16,11 +16,11 @@ import ctypes
 import os
 from fractions import Fraction
 
-import numpy as np
 import torch
 
+import fldr_model
 import fldr_video
-from fldr_video import Format, Frame, IO, empty_frame, frame_struct, plane_dtype, plane_shapes  # noqa: F401
+from fldr_video import Format, Frame, IO, _stream_ptr, empty_frame, frame_struct, plane_dtype, plane_shapes  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfldr_rate.so")
@@ -82,19 +82,7 @@ def lib():
     """The loaded libfldr_rate.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError("%s is missing — build it with `make -C fldr-vfi_amd/csrc` (or __graft_entry__.build())" % LIB_PATH)
-        l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = res, args
-        for which, cls in enumerate((SceneParams, SceneResult, RateConfig)):
-            if l.fldr_rate_sizeof(which) != ctypes.sizeof(cls):
-                raise ImportError("%s: sizeof(%s) is %d in the library, %d in this binding" % (LIB_PATH, cls.__name__, l.fldr_rate_sizeof(which),
-                                                                                              ctypes.sizeof(cls)))
-        if l.fldr_rate_version() != RATE_VERSION:
-            raise ImportError("%s reports version %d, this binding is written for %d: rebuild it" % (LIB_PATH, l.fldr_rate_version(), RATE_VERSION))
-        _lib = l
+        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (SceneParams, SceneResult, RateConfig), "fldr_rate", RATE_VERSION)
     return _lib
 
 
@@ -138,11 +126,6 @@ def schedule(n_frames, in_rate, out_rate):
 
 
 # ---- the cut measure ------------------------------------------------------------------------------------------------------------------
-def _stream_ptr(device, stream):
-    st = stream if stream is not None else torch.cuda.current_stream(device)
-    return ctypes.c_void_p(st.cuda_stream)
-
-
 def scene_state(device):
     """FLDR_SCENE_STATE_BYTES of device memory (torch's allocations are 256-byte aligned)."""
     return torch.empty(SCENE_STATE_BYTES, dtype=torch.uint8, device=device)
@@ -205,10 +188,7 @@ class NativeRate(fldr_video.NativeVideo):
         skips the synchronising read-back and returns the state tensor in its place."""
         fmt = fmt or Format()
         H, W = frames[0][0].shape
-        if torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous():
-            tt = t
-        else:
-            tt = torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device)
+        tt = self._t(t)
         n_t = tt.numel()
         if params is not None and not isinstance(params, SceneParams):
             params = SceneParams(*params)
@@ -222,9 +202,11 @@ class NativeRate(fldr_video.NativeVideo):
         return outs, (read_result(state) if read else state)
 
 
-class Converter:
+class Converter(fldr_video.HostStream):
     """fldr_rate: host frames (tuples of numpy planes) pushed one by one at in_rate; each push returns the output frames at out_rate that
     fall before the pushed frame (schedule()), flush() the one that lands on the last frame."""
+
+    _destroy = staticmethod(lambda h: lib().fldr_rate_destroy(h))
 
     def __init__(self, native_model, H, W, fmt=None, in_rate=24, out_rate=60, scene=True, params=None):
         fmt = fmt or Format()
@@ -240,11 +222,8 @@ class Converter:
         _check(lib().fldr_rate_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_rate_create")
         self.H, self.W, self.format = int(H), int(W), fmt
         self.max_out = lib().fldr_rate_max_out(self._h)
-        self._outs = [tuple(np.empty(s, plane_dtype(fmt, numpy=True)) for s in plane_shapes(fmt, H, W)) for _ in range(self.max_out)]
+        self._stage(fmt, H, W, self.max_out)
         self.last_scene = None
-
-    def _out_structs(self):
-        return (Frame * self.max_out)(*[frame_struct(o) for o in self._outs])
 
     def push(self, frame):
         """-> the list of output frames due (tuples of numpy planes, fresh copies); self.last_scene: the pair's scene dict."""
@@ -253,23 +232,12 @@ class Converter:
         res = SceneResult()
         _check(lib().fldr_rate_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n), ctypes.byref(res)), "fldr_rate_push")
         self.last_scene = res.as_dict()
-        return [tuple(p.copy() for p in o) for o in self._outs[:n.value]]
+        return self._taken(n.value)
 
     def flush(self):
         n = ctypes.c_int(-1)
         _check(lib().fldr_rate_flush(self._h, self._out_structs(), ctypes.byref(n)), "fldr_rate_flush")
-        return [tuple(p.copy() for p in o) for o in self._outs[:n.value]]
+        return self._taken(n.value)
 
     def reset(self):
         _check(lib().fldr_rate_reset(self._h), "fldr_rate_reset")
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().fldr_rate_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

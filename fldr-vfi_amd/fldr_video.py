@@ -104,19 +104,7 @@ def lib():
     """The loaded libfldr_video.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
     global _lib
     if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError("%s is missing — build it with `make -C fldr-vfi_amd/csrc` (or __graft_entry__.build())" % LIB_PATH)
-        l = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGNATURES.items():
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = res, args
-        for which, cls in enumerate((Format, Frame, IO, SessionConfig)):
-            if l.fldr_video_sizeof(which) != ctypes.sizeof(cls):
-                raise ImportError("%s: sizeof(%s) is %d in the library, %d in this binding" % (LIB_PATH, cls.__name__, l.fldr_video_sizeof(which),
-                                                                                              ctypes.sizeof(cls)))
-        if l.fldr_video_version() != VIDEO_VERSION:
-            raise ImportError("%s reports version %d, this binding is written for %d: rebuild it" % (LIB_PATH, l.fldr_video_version(), VIDEO_VERSION))
-        _lib = l
+        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (Format, Frame, IO, SessionConfig), "fldr_video", VIDEO_VERSION)
     return _lib
 
 
@@ -130,15 +118,7 @@ def test_hooks():
     library stays what lib() returns: the two are separate handles in one process."""
     global _hooks_lib
     if _hooks_lib is None:
-        if not os.path.exists(TEST_LIB_PATH):
-            raise ImportError("%s is missing — build it with `make -C fldr-vfi_amd/csrc` (or __graft_entry__.build())" % TEST_LIB_PATH)
-        l = ctypes.CDLL(TEST_LIB_PATH)
-        for name, (res, args) in list(_SIGNATURES.items()) + list(_HOOK_SIGNATURES.items()):
-            fn = getattr(l, name)
-            fn.restype, fn.argtypes = res, args
-        if l.fldr_video_version() != VIDEO_VERSION:
-            raise ImportError("%s reports version %d, this binding is written for %d: rebuild it" % (TEST_LIB_PATH, l.fldr_video_version(), VIDEO_VERSION))
-        _hooks_lib = l
+        _hooks_lib = fldr_model.load_library(TEST_LIB_PATH, {**_SIGNATURES, **_HOOK_SIGNATURES}, (), "fldr_video", VIDEO_VERSION)
     return _hooks_lib
 
 
@@ -181,12 +161,13 @@ def empty_frame(layout, H, W, device):
     return tuple(torch.empty(r, c, dtype=plane_dtype(layout), device=device) for r, c in plane_shapes(layout, H, W))
 
 
-# ---- the converters alone (test build) ----------------------------------------------------------------------------------------------
 def _stream_ptr(device, stream):
+    """The hipStream_t of `stream` (a torch.cuda.Stream), or of torch's current stream of `device` when None."""
     st = stream if stream is not None else torch.cuda.current_stream(device)
     return ctypes.c_void_p(st.cuda_stream)
 
 
+# ---- the converters alone (test build) ----------------------------------------------------------------------------------------------
 def debug_to_planar(frames, fmt, pair=None, stream=None):
     """fldr_video_debug_to_planar: frames (I0, I1), each a tuple of device plane tensors in `fmt` (pitches from their strides) -> the
     planar BGR pair [2,3,H,W] (uint8; uint16 at depth 10; `pair` when given).  Enqueues on torch's current stream."""
@@ -249,9 +230,14 @@ class NativeVideo:
 
     def forward_io(self, io, ws, stream=None):
         """The raw call; returns the code without raising (tests of the error contract)."""
-        st = stream if stream is not None else torch.cuda.current_stream(self.device)
         return lib().fldr_video_forward(self.model._h, ctypes.byref(io), ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
-                                        ws.numel() if ws is not None else 0, ctypes.c_void_p(st.cuda_stream))
+                                        ws.numel() if ws is not None else 0, _stream_ptr(self.device, stream))
+
+    def _t(self, t):
+        """t as the float32 device tensor a forward reads: one that already is (contiguous, on a device) is used in place."""
+        if torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous():
+            return t
+        return torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device)
 
     def make_io(self, frames, t, in_format, out_format, outs, H, W):
         io = IO()
@@ -270,10 +256,7 @@ class NativeVideo:
         in_format = in_format or Format()
         out_format = out_format or Format(in_format.layout, in_format.matrix, in_format.range, in_format.depth)
         H, W = frames[0][0].shape
-        if torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous():
-            tt = t
-        else:
-            tt = torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device)
+        tt = self._t(t)
         n_t = tt.numel()
         if outs is None:
             outs = [empty_frame(out_format, H, W, self.device) for _ in range(n_t)]
@@ -284,8 +267,37 @@ class NativeVideo:
         return outs
 
 
-class Session:
+class HostStream:
+    """What Session and fldr_rate.Converter share: the lifetime of the handle `_h` (a subclass names the library's `_destroy`) and the
+    host planes the library writes a push's output frames into."""
+    _h = None
+
+    def _stage(self, fmt, H, W, n):
+        self._outs = [tuple(np.empty(s, plane_dtype(fmt, numpy=True)) for s in plane_shapes(fmt, H, W)) for _ in range(n)]
+
+    def _out_structs(self):
+        return (Frame * len(self._outs))(*[frame_struct(o) for o in self._outs])
+
+    def _taken(self, n):
+        """The first n staged frames as fresh copies."""
+        return [tuple(p.copy() for p in o) for o in self._outs[:n]]
+
+    def close(self):
+        if self._h is not None and self._h.value:
+            self._destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Session(HostStream):
     """fldr_video_session: host frames (tuples of numpy planes) pushed one by one; each push after the first returns n_t frames."""
+
+    _destroy = staticmethod(lambda h: lib().fldr_video_session_destroy(h))
 
     def __init__(self, native_model, H, W, n_t=1, in_format=None, out_format=None, t=None):
         in_format = in_format or Format()
@@ -300,27 +312,15 @@ class Session:
         self.model = native_model                                    # the session uses the model: keep it alive
         _check(lib().fldr_video_session_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_video_session_create")
         self.H, self.W, self.n_t, self.in_format, self.out_format = int(H), int(W), int(n_t), in_format, out_format
-        self._outs = [tuple(np.empty(s, plane_dtype(out_format, numpy=True)) for s in plane_shapes(out_format, H, W)) for _ in range(n_t)]
+        self._stage(out_format, H, W, n_t)
 
     def push(self, frame):
         """-> [] or a list of n_t output frames (tuples of numpy planes, fresh copies)."""
         fr = frame_struct(frame)
-        outs = (Frame * self.n_t)(*[frame_struct(o) for o in self._outs])
         n = ctypes.c_int(-1)
-        _check(lib().fldr_video_session_push(self._h, ctypes.byref(fr), outs, ctypes.byref(n)), "fldr_video_session_push")
+        _check(lib().fldr_video_session_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n)), "fldr_video_session_push")
         self.last_n_out = n.value
-        return [tuple(p.copy() for p in o) for o in self._outs[:n.value]]
+        return self._taken(n.value)
 
     def reset(self):
         _check(lib().fldr_video_session_reset(self._h), "fldr_video_session_reset")
-
-    def close(self):
-        if self._h is not None and self._h.value:
-            lib().fldr_video_session_destroy(self._h)
-        self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

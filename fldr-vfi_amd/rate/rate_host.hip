@@ -1,44 +1,18 @@
 // libfldr_rate.so, host side: validation, fldr_scene_measure, fldr_rate_forward (measure -> fldr_video_forward -> select) and the rate
-// converter for streams of host frames.  The only fldr_* functions called are those of fldr_video.h and fldr_model.h.
+// converter for streams of host frames.  The video API's rules for formats and frames, and the stream / device block / pinned block the
+// converter owns, come from ../video/frame_host.h.  The only fldr_* functions called are those of fldr_video.h and fldr_model.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <new>
 #include <vector>
 
+#include "../video/frame_host.h"
 #include "rate_internal.h"
 
 using namespace fldr_rate_impl;
 
 namespace {
-
-constexpr int64_t ALIGN = 256;
-int64_t align_up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
-
-// ---- the video API's rules for formats and frames (fldr_video_forward applies the same ones) ----------------------------------------
-int planes_of(int layout) { return layout == FLDR_VIDEO_NV12 ? 2 : 3; }
-bool deep(const fldr_video_format& f) { return f.depth == 10; }
-
-int check_format(const fldr_video_format& f) {
-    if ((unsigned)f.layout > 1u || (unsigned)f.matrix > 1u || (unsigned)f.range > 1u) return FLDR_VIDEO_E_FORMAT;
-    if (f.depth != 0 && f.depth != 8 && f.depth != 10) return FLDR_VIDEO_E_FORMAT;
-    for (int i = 0; i < 4; ++i) if (f.reserved[i]) return FLDR_VIDEO_E_FORMAT;
-    return 0;
-}
-
-int64_t row_bytes(const fldr_video_format& f, int p, int W) {
-    const int64_t cw = (W + 1) / 2, b = deep(f) ? 2 : 1;
-    return b * (p == 0 ? W : (f.layout == FLDR_VIDEO_NV12 ? 2 * cw : cw));
-}
-
-int rows_of(int p, int H) { return p == 0 ? H : (H + 1) / 2; }
-
-int check_frame(const fldr_video_frame& fr, const fldr_video_format& f, int W) {
-    for (int p = 0; p < planes_of(f.layout); ++p) if (!fr.plane[p] || (deep(f) && ((uintptr_t)fr.plane[p] & 1))) return FLDR_VIDEO_E_PLANE;
-    for (int p = 0; p < planes_of(f.layout); ++p)
-        if (fr.pitch[p] < row_bytes(f, p, W) || (deep(f) && (fr.pitch[p] & 1))) return FLDR_VIDEO_E_PITCH;
-    return 0;
-}
 
 bool same_format(const fldr_video_format& a, const fldr_video_format& b) {
     return a.layout == b.layout && a.matrix == b.matrix && a.range == b.range && deep(a) == deep(b);
@@ -72,8 +46,6 @@ int enqueue_measure(int H, int W, const fldr_video_format& fmt, const fldr_video
     const int mode = !deep(fmt) ? Y8_BYTE : fmt.layout == FLDR_VIDEO_NV12 ? Y8_P010 : Y8_LOW10;
     return scene_measure(in[0].plane[0], in[0].pitch[0], in[1].plane[0], in[1].pitch[0], H, W, mode, sad_pm, hist_pm, state, s);
 }
-
-#define CK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
 
 }  // namespace
 
@@ -148,12 +120,11 @@ extern "C" FLDR_RATE_API int fldr_rate_forward(const fldr_model* m, const fldr_v
 struct fldr_rate {
     const fldr_model* model;
     fldr_rate_config cfg;
-    int device;
     int64_t A, B;                      // output j at input position j A / B
     int max_out;
-    hipStream_t stream;
-    char* mem;                         // device: slot 0, slot 1, max_out outputs, t, scene state (pairs without a forward), workspace
-    uint8_t* pinned;                   // host: two input frames (the held one and the new one), max_out output frames, t, the scene result
+    // device: slot 0, slot 1, max_out outputs, t, scene state (pairs without a forward), workspace
+    // pinned: two input frames (the held one and the new one), max_out output frames, t, the scene result
+    StreamMem sm;
     int64_t frame_bytes, ws_bytes;
     uint8_t* slot[2];
     uint8_t* out_dev;
@@ -170,53 +141,6 @@ struct fldr_rate {
 };
 
 namespace {
-
-struct DeviceGuard {                                      // make `dev` current, restore the caller's device on exit
-    int prev = -1;
-    int rc = 0;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) rc = FLDR_RATE_E_DEVICE;
-    }
-    ~DeviceGuard() { if (prev >= 0) { int cur = -1; if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev); } }
-};
-
-// packed planes of one frame (pitch = row bytes) starting at `base`
-fldr_video_frame packed(uint8_t* base, const fldr_video_format& fmt, int H, int W) {
-    fldr_video_frame f;
-    memset(&f, 0, sizeof(f));
-    int64_t off = 0;
-    for (int p = 0; p < planes_of(fmt.layout); ++p) {
-        f.plane[p] = base + off;
-        f.pitch[p] = row_bytes(fmt, p, W);
-        off += f.pitch[p] * rows_of(p, H);
-    }
-    return f;
-}
-
-int64_t frame_size(const fldr_video_format& fmt, int H, int W) {
-    int64_t n = 0;
-    for (int p = 0; p < planes_of(fmt.layout); ++p) n += row_bytes(fmt, p, W) * rows_of(p, H);
-    return n;
-}
-
-// rows of every plane from `src` (any pitches) to `dst` (any pitches), on the host
-void copy_planes(const fldr_video_frame& dst, const fldr_video_frame& src, const fldr_video_format& fmt, int H, int W) {
-    for (int p = 0; p < planes_of(fmt.layout); ++p) {
-        const int64_t rb = row_bytes(fmt, p, W), n = rows_of(p, H);
-        for (int64_t r = 0; r < n; ++r)
-            memcpy((uint8_t*)dst.plane[p] + r * dst.pitch[p], (const uint8_t*)src.plane[p] + r * src.pitch[p], (size_t)rb);
-    }
-}
-
-void release(fldr_rate* s) {
-    DeviceGuard g(s->device);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    if (s->mem) (void)hipFree(s->mem);
-    if (s->pinned) (void)hipHostFree(s->pinned);
-    (void)hipGetLastError();
-    delete s;
-}
 
 int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
 
@@ -247,27 +171,22 @@ extern "C" FLDR_RATE_API int fldr_rate_create(const fldr_model* m, const fldr_ra
     if (!s) return FLDR_RATE_E_DEVICE;
     s->model = m;
     s->cfg = *cfg;
-    s->device = cfg->device;
     s->A = A; s->B = B; s->max_out = max_out;
     s->prev = -1; s->n = 0; s->j = 0;
-    s->frame_bytes = align_up(frame_size(cfg->format, H, W));
+    s->frame_bytes = align_up(packed_bytes(cfg->format, H, W));
     s->ws_bytes = wsb;
-    DeviceGuard guard(s->device);
-    if (guard.rc) { delete s; return guard.rc; }
     const int64_t t_bytes = align_up(4ll * max_out);
     const int64_t dev_total = (2 + max_out) * s->frame_bytes + t_bytes + FLDR_SCENE_STATE_BYTES + wsb;
     const int64_t host_total = (2 + max_out) * s->frame_bytes + t_bytes + ALIGN;
-    if (hipMalloc((void**)&s->mem, (size_t)dev_total) != hipSuccess) { s->mem = nullptr; release(s); return FLDR_RATE_E_DEVICE; }
-    if (hipHostMalloc((void**)&s->pinned, (size_t)host_total, hipHostMallocDefault) != hipSuccess) { s->pinned = nullptr; release(s); return FLDR_RATE_E_DEVICE; }
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { s->stream = nullptr; release(s); return FLDR_RATE_E_DEVICE; }
-    s->slot[0] = (uint8_t*)s->mem;
+    if (!open_stream_mem(s->sm, cfg->device, dev_total, host_total)) { delete s; return FLDR_RATE_E_DEVICE; }
+    s->slot[0] = s->sm.dev;
     s->slot[1] = s->slot[0] + s->frame_bytes;
     s->out_dev = s->slot[1] + s->frame_bytes;
     s->t_dev = (float*)(s->out_dev + max_out * s->frame_bytes);
     s->state_dev = (char*)s->t_dev + t_bytes;
     s->ws = (char*)s->state_dev + FLDR_SCENE_STATE_BYTES;
-    s->in_host[0] = s->pinned;
-    s->in_host[1] = s->pinned + s->frame_bytes;
+    s->in_host[0] = s->sm.pinned;
+    s->in_host[1] = s->in_host[0] + s->frame_bytes;
     s->out_host = s->in_host[1] + s->frame_bytes;
     s->t_host = (float*)(s->out_host + max_out * s->frame_bytes);
     s->scene_host = (fldr_scene_result*)((char*)s->t_host + t_bytes);
@@ -300,11 +219,11 @@ extern "C" FLDR_RATE_API int fldr_rate_push(fldr_rate* s, const fldr_video_frame
         if (!host_outs) return FLDR_RATE_E_ARG;
         for (int k = 0; k < count; ++k) CK(check_frame(host_outs[k], fmt, W));
     }
-    DeviceGuard g(s->device);
-    if (g.rc) return g.rc;
+    DeviceGuard g(s->sm.device);
+    if (!g.ok) return FLDR_RATE_E_DEVICE;
+    const hipStream_t stream = s->sm.stream;
     const int cur = s->prev == 0 ? 1 : 0;                          // the slot not holding the previous frame
-    copy_planes(packed(s->in_host[cur], fmt, H, W), *frame, fmt, H, W);
-    hipError_t e = hipMemcpyAsync(s->slot[cur], s->in_host[cur], (size_t)s->frame_bytes, hipMemcpyHostToDevice, s->stream);
+    hipError_t e = upload_frame(s->sm, s->slot[cur], s->in_host[cur], s->frame_bytes, *frame, fmt, H, W);
     int rc = e == hipSuccess ? 0 : (int)e;
     const bool measure = pair && c.scene == 1;
     if (!rc && pair && (n_t || measure)) {
@@ -312,7 +231,7 @@ extern "C" FLDR_RATE_API int fldr_rate_push(fldr_rate* s, const fldr_video_frame
         void* state = s->state_dev;
         if (n_t) {
             for (int k = 0, q = 0; k < count; ++k) if (r_of[k]) s->t_host[q++] = (float)r_of[k] / (float)s->B;
-            e = hipMemcpyAsync(s->t_dev, s->t_host, 4ull * n_t, hipMemcpyHostToDevice, s->stream);
+            e = hipMemcpyAsync(s->t_dev, s->t_host, 4ull * n_t, hipMemcpyHostToDevice, stream);
             if (e != hipSuccess) rc = (int)e;
             std::vector<fldr_video_frame> outs((size_t)n_t);
             for (int k = 0; k < n_t; ++k) outs[k] = packed(s->out_dev + k * s->frame_bytes, fmt, H, W);
@@ -325,29 +244,29 @@ extern "C" FLDR_RATE_API int fldr_rate_push(fldr_rate* s, const fldr_video_frame
             if (!rc && measure) {
                 // the forward always runs; on a cut the select of fldr_rate_forward overwrites its outputs on the device
                 const int64_t need = fldr_rate_workspace_bytes(s->model, H, W, n_t);
-                rc = need < 0 ? (int)need : fldr_rate_forward(s->model, &io, &c.scene_params, s->ws, s->ws_bytes, s->stream);
+                rc = need < 0 ? (int)need : fldr_rate_forward(s->model, &io, &c.scene_params, s->ws, s->ws_bytes, stream);
                 state = (char*)s->ws + need - FLDR_SCENE_STATE_BYTES;
             } else if (!rc) {
-                rc = fldr_video_forward(s->model, &io, s->ws, s->ws_bytes, s->stream);
+                rc = fldr_video_forward(s->model, &io, s->ws, s->ws_bytes, stream);
             }
             if (!rc) {
-                e = hipMemcpyAsync(s->out_host, s->out_dev, (size_t)(n_t * s->frame_bytes), hipMemcpyDeviceToHost, s->stream);
+                e = hipMemcpyAsync(s->out_host, s->out_dev, (size_t)(n_t * s->frame_bytes), hipMemcpyDeviceToHost, stream);
                 if (e != hipSuccess) rc = (int)e;
             }
         } else {
-            rc = fldr_scene_measure(H, W, &fmt, in, &c.scene_params, state, s->stream);        // a pair without an interpolated output
+            rc = fldr_scene_measure(H, W, &fmt, in, &c.scene_params, state, stream);        // a pair without an interpolated output
         }
         if (!rc && measure) {
-            e = hipMemcpyAsync(s->scene_host, state, sizeof(fldr_scene_result), hipMemcpyDeviceToHost, s->stream);
+            e = hipMemcpyAsync(s->scene_host, state, sizeof(fldr_scene_result), hipMemcpyDeviceToHost, stream);
             if (e != hipSuccess) rc = (int)e;
         }
     }
-    e = hipStreamSynchronize(s->stream);
+    e = hipStreamSynchronize(stream);
     if (!rc && e != hipSuccess) rc = (int)e;
     if (rc) { s->prev = -1; s->n = 0; s->j = 0; return rc; }     // the held frame is not to be trusted: as after a reset
     for (int k = 0, q = 0; k < count; ++k) {
-        if (r_of[k]) copy_planes(host_outs[k], packed(s->out_host + (q++) * s->frame_bytes, fmt, H, W), fmt, H, W);
-        else copy_planes(host_outs[k], packed(s->in_host[s->prev], fmt, H, W), fmt, H, W);                        // frame n - 1, its bytes
+        if (r_of[k]) unpack_frame(host_outs[k], s->out_host + (q++) * s->frame_bytes, fmt, H, W);
+        else unpack_frame(host_outs[k], s->in_host[s->prev], fmt, H, W);                                          // frame n - 1, its bytes
     }
     if (measure && scene) *scene = *s->scene_host;
     *n_out = count;
@@ -364,7 +283,7 @@ extern "C" FLDR_RATE_API int fldr_rate_flush(fldr_rate* s, const fldr_video_fram
     if (!host_outs) return FLDR_RATE_E_ARG;
     const fldr_rate_config& c = s->cfg;
     CK(check_frame(host_outs[0], c.format, c.W));
-    copy_planes(host_outs[0], packed(s->in_host[s->prev], c.format, c.H, c.W), c.format, c.H, c.W);
+    unpack_frame(host_outs[0], s->in_host[s->prev], c.format, c.H, c.W);
     s->j += 1;
     *n_out = 1;
     return 0;
@@ -377,5 +296,5 @@ extern "C" FLDR_RATE_API int fldr_rate_reset(fldr_rate* s) {
 }
 
 extern "C" FLDR_RATE_API void fldr_rate_destroy(fldr_rate* s) {
-    if (s) release(s);
+    if (s) { close_stream_mem(s->sm); delete s; }
 }

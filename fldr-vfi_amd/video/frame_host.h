@@ -1,0 +1,128 @@
+// The host side of the frame contract of include/fldr_video.h (what a valid format and a valid frame are, how large a plane is) and the
+// plumbing of a stream object (fldr_video_session, fldr_rate): a device, a stream, one device block, one pinned block, packed frames in
+// them.  Included by video_host.hip and by ../rate/rate_host.hip: libfldr_rate.so refuses exactly the frames libfldr_video.so refuses
+// because both compile this text.  Everything is in the unnamed namespace: nothing here becomes a symbol of either library.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstring>
+
+#include "fldr_video.h"
+
+namespace {
+
+constexpr int64_t ALIGN = 256;
+int64_t align_up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
+
+#define CK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
+
+// ---- formats and frames -----------------------------------------------------------------------------------------------------------
+int planes_of(int layout) { return layout == FLDR_VIDEO_NV12 ? 2 : 3; }
+
+bool deep(const fldr_video_format& f) { return f.depth == 10; }       // 16-bit words (depth 0 is an alias of 8)
+
+int check_format(const fldr_video_format& f) {
+    if ((unsigned)f.layout > 1u || (unsigned)f.matrix > 1u || (unsigned)f.range > 1u) return FLDR_VIDEO_E_FORMAT;
+    if (f.depth != 0 && f.depth != 8 && f.depth != 10) return FLDR_VIDEO_E_FORMAT;
+    for (int i = 0; i < 4; ++i) if (f.reserved[i]) return FLDR_VIDEO_E_FORMAT;
+    return 0;
+}
+
+// bytes per row of plane p of a frame of width W
+int64_t row_bytes(const fldr_video_format& f, int p, int W) {
+    const int64_t cw = (W + 1) / 2, b = deep(f) ? 2 : 1;
+    return b * (p == 0 ? W : (f.layout == FLDR_VIDEO_NV12 ? 2 * cw : cw));
+}
+
+int rows_of(int p, int H) { return p == 0 ? H : (H + 1) / 2; }
+
+int check_frame(const fldr_video_frame& fr, const fldr_video_format& f, int W) {
+    for (int p = 0; p < planes_of(f.layout); ++p) if (!fr.plane[p] || (deep(f) && ((uintptr_t)fr.plane[p] & 1))) return FLDR_VIDEO_E_PLANE;
+    for (int p = 0; p < planes_of(f.layout); ++p)
+        if (fr.pitch[p] < row_bytes(f, p, W) || (deep(f) && (fr.pitch[p] & 1))) return FLDR_VIDEO_E_PITCH;
+    return 0;
+}
+
+// ---- packed frames ----------------------------------------------------------------------------------------------------------------
+// packed planes of one frame (pitch = row bytes) starting at `base`
+fldr_video_frame packed(uint8_t* base, const fldr_video_format& fmt, int H, int W) {
+    fldr_video_frame f;
+    memset(&f, 0, sizeof(f));
+    int64_t off = 0;
+    for (int p = 0; p < planes_of(fmt.layout); ++p) {
+        f.plane[p] = base + off;
+        f.pitch[p] = row_bytes(fmt, p, W);
+        off += f.pitch[p] * rows_of(p, H);
+    }
+    return f;
+}
+
+int64_t packed_bytes(const fldr_video_format& fmt, int H, int W) {
+    int64_t n = 0;
+    for (int p = 0; p < planes_of(fmt.layout); ++p) n += row_bytes(fmt, p, W) * rows_of(p, H);
+    return n;
+}
+
+// rows of every plane from `src` (any pitches) to `dst` (any pitches), on the host
+void copy_planes(const fldr_video_frame& dst, const fldr_video_frame& src, const fldr_video_format& fmt, int H, int W) {
+    for (int p = 0; p < planes_of(fmt.layout); ++p) {
+        const int64_t rb = row_bytes(fmt, p, W), n = rows_of(p, H);
+        for (int64_t r = 0; r < n; ++r)
+            memcpy((uint8_t*)dst.plane[p] + r * dst.pitch[p], (const uint8_t*)src.plane[p] + r * src.pitch[p], (size_t)rb);
+    }
+}
+
+// ---- a device, a stream on it, one device block, one pinned block -------------------------------------------------------------------
+struct DeviceGuard {                                      // make `dev` current, restore the caller's device on exit
+    int prev = -1;
+    bool ok = true;
+    explicit DeviceGuard(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (prev != dev && hipSetDevice(dev) != hipSuccess) ok = false;
+    }
+    ~DeviceGuard() { if (prev >= 0) { int cur = -1; if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev); } }
+};
+
+struct StreamMem {
+    int device = -1;
+    hipStream_t stream = nullptr;      // non-blocking
+    uint8_t* dev = nullptr;
+    uint8_t* pinned = nullptr;
+};
+
+void close_stream_mem(StreamMem& m) {
+    DeviceGuard g(m.device);
+    if (m.stream) (void)hipStreamDestroy(m.stream);
+    if (m.dev) (void)hipFree(m.dev);
+    if (m.pinned) (void)hipHostFree(m.pinned);
+    (void)hipGetLastError();
+    m = StreamMem();
+}
+
+// all of it or nothing: false (no such device, out of memory) leaves `m` empty
+bool open_stream_mem(StreamMem& m, int device, int64_t dev_bytes, int64_t pinned_bytes) {
+    m = StreamMem();
+    m.device = device;
+    DeviceGuard g(device);
+    if (g.ok && hipMalloc((void**)&m.dev, (size_t)dev_bytes) == hipSuccess &&
+        hipHostMalloc((void**)&m.pinned, (size_t)pinned_bytes, hipHostMallocDefault) == hipSuccess &&
+        hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking) == hipSuccess)
+        return true;
+    close_stream_mem(m);
+    return false;
+}
+
+// one host frame (any pitches) -> packed in `pinned_slot` -> enqueued to `dev_slot`; the pinned copy stays valid for the caller
+hipError_t upload_frame(const StreamMem& m, uint8_t* dev_slot, uint8_t* pinned_slot, int64_t slot_bytes, const fldr_video_frame& src,
+                        const fldr_video_format& fmt, int H, int W) {
+    copy_planes(packed(pinned_slot, fmt, H, W), src, fmt, H, W);
+    return hipMemcpyAsync(dev_slot, pinned_slot, (size_t)slot_bytes, hipMemcpyHostToDevice, m.stream);
+}
+
+// one packed frame in the pinned block -> the caller's planes
+void unpack_frame(const fldr_video_frame& dst, uint8_t* pinned_slot, const fldr_video_format& fmt, int H, int W) {
+    copy_planes(dst, packed(pinned_slot, fmt, H, W), fmt, H, W);
+}
+
+}  // namespace

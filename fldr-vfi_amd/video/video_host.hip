@@ -1,47 +1,18 @@
-// libfldr_video.so, host side: validation, the workspace layout, fldr_video_forward (input conversion -> one fldr_model_forward ->
-// n_t output conversions) and the session API for streams of host frames.  The only fldr_* functions called are those of
-// fldr_model.h.
+// libfldr_video.so, host side: the workspace layout, fldr_video_forward (input conversion -> one fldr_model_forward -> n_t output
+// conversions) and the session API for streams of host frames.  What a valid format and frame are, and the stream / device block / pinned
+// block a session owns, are in frame_host.h (shared with libfldr_rate.so).  The only fldr_* functions called are those of fldr_model.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <new>
 #include <vector>
 
+#include "frame_host.h"
 #include "video_internal.h"
 
 using namespace fldr_video_impl;
 
 namespace {
-
-constexpr int64_t ALIGN = 256;
-int64_t align_up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
-
-int planes_of(int layout) { return layout == FLDR_VIDEO_NV12 ? 2 : 3; }
-
-int check_format(const fldr_video_format& f) {
-    if ((unsigned)f.layout > 1u || (unsigned)f.matrix > 1u || (unsigned)f.range > 1u) return FLDR_VIDEO_E_FORMAT;
-    if (f.depth != 0 && f.depth != 8 && f.depth != 10) return FLDR_VIDEO_E_FORMAT;
-    for (int i = 0; i < 4; ++i) if (f.reserved[i]) return FLDR_VIDEO_E_FORMAT;
-    return 0;
-}
-
-bool deep(const fldr_video_format& f) { return f.depth == 10; }       // 16-bit words
-
-// bytes per row of plane p of a frame of width W
-int64_t row_bytes(int layout, int depth, int p, int W) {
-    const int64_t cw = (W + 1) / 2, b = depth == 10 ? 2 : 1;
-    return b * (p == 0 ? W : (layout == FLDR_VIDEO_NV12 ? 2 * cw : cw));
-}
-
-int64_t rows_of(int p, int H) { return p == 0 ? H : (H + 1) / 2; }
-
-int check_frame(const fldr_video_frame& fr, const fldr_video_format& f, int W) {
-    const int layout = f.layout;
-    for (int p = 0; p < planes_of(layout); ++p) if (!fr.plane[p] || (deep(f) && ((uintptr_t)fr.plane[p] & 1))) return FLDR_VIDEO_E_PLANE;
-    for (int p = 0; p < planes_of(layout); ++p)
-        if (fr.pitch[p] < row_bytes(layout, f.depth, p, W) || (deep(f) && (fr.pitch[p] & 1))) return FLDR_VIDEO_E_PITCH;
-    return 0;
-}
 
 // host-only checks of a forward's arguments (no model, no device)
 int validate_io(const fldr_video_io* io) {
@@ -71,8 +42,6 @@ int64_t plan(const fldr_model* m, int H, int W, int n_t, int in_bytes, int out_b
 }
 
 const YuvCoeffs& coeffs(const fldr_video_format& f) { return deep(f) ? YUV_COEFFS_10[f.matrix][f.range] : YUV_COEFFS[f.matrix][f.range]; }
-
-#define CK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
 
 }  // namespace
 
@@ -139,10 +108,7 @@ extern "C" FLDR_VIDEO_API int fldr_video_forward(const fldr_model* m, const fldr
 struct fldr_video_session {
     const fldr_model* model;
     fldr_video_session_config cfg;
-    int device;
-    hipStream_t stream;
-    char* mem;                         // device: slot 0, slot 1, n_t outputs, t, workspace
-    uint8_t* pinned;                   // host: one input frame, n_t output frames (packed planes)
+    StreamMem sm;                      // device: slot 0, slot 1, n_t outputs, t, workspace; pinned: one input frame, n_t output frames (packed)
     int64_t in_bytes, out_bytes, ws_bytes;
     uint8_t* slot[2];
     uint8_t* out_dev;
@@ -150,58 +116,6 @@ struct fldr_video_session {
     void* ws;
     int prev;                          // slot holding the previous frame, -1 when none
 };
-
-namespace {
-
-struct DeviceGuard {                                      // make `dev` current, restore the caller's device on exit
-    int prev = -1;
-    int rc = 0;
-    explicit DeviceGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev && hipSetDevice(dev) != hipSuccess) rc = FLDR_VIDEO_E_DEVICE;
-    }
-    ~DeviceGuard() { if (prev >= 0) { int cur = -1; if (hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev); } }
-};
-
-// packed planes of one frame (pitch = row bytes) starting at `base`
-fldr_video_frame packed(uint8_t* base, const fldr_video_format& fmt, int H, int W) {
-    const int layout = fmt.layout;
-    fldr_video_frame f;
-    memset(&f, 0, sizeof(f));
-    int64_t off = 0;
-    for (int p = 0; p < planes_of(layout); ++p) {
-        f.plane[p] = base + off;
-        f.pitch[p] = row_bytes(layout, fmt.depth, p, W);
-        off += f.pitch[p] * rows_of(p, H);
-    }
-    return f;
-}
-
-int64_t frame_bytes(const fldr_video_format& fmt, int H, int W) {
-    int64_t n = 0;
-    for (int p = 0; p < planes_of(fmt.layout); ++p) n += row_bytes(fmt.layout, fmt.depth, p, W) * rows_of(p, H);
-    return n;
-}
-
-// rows of every plane from `src` (any pitches) to `dst` (any pitches), on the host
-void copy_planes(const fldr_video_frame& dst, const fldr_video_frame& src, const fldr_video_format& fmt, int H, int W) {
-    for (int p = 0; p < planes_of(fmt.layout); ++p) {
-        const int64_t rb = row_bytes(fmt.layout, fmt.depth, p, W), n = rows_of(p, H);
-        for (int64_t r = 0; r < n; ++r)
-            memcpy((uint8_t*)dst.plane[p] + r * dst.pitch[p], (const uint8_t*)src.plane[p] + r * src.pitch[p], (size_t)rb);
-    }
-}
-
-void release(fldr_video_session* s) {
-    DeviceGuard g(s->device);
-    if (s->stream) (void)hipStreamDestroy(s->stream);
-    if (s->mem) (void)hipFree(s->mem);
-    if (s->pinned) (void)hipHostFree(s->pinned);
-    (void)hipGetLastError();
-    delete s;
-}
-
-}  // namespace
 
 extern "C" FLDR_VIDEO_API int fldr_video_session_create(const fldr_model* m, const fldr_video_session_config* cfg, fldr_video_session** out) {
     if (!cfg || !out) return FLDR_VIDEO_E_ARG;
@@ -221,28 +135,24 @@ extern "C" FLDR_VIDEO_API int fldr_video_session_create(const fldr_model* m, con
     s->model = m;
     s->cfg = *cfg;
     s->cfg.t = nullptr;
-    s->device = cfg->device;
     s->prev = -1;
-    s->in_bytes = align_up(frame_bytes(cfg->in_format, H, W));
-    s->out_bytes = align_up(frame_bytes(cfg->out_format, H, W));
+    s->in_bytes = align_up(packed_bytes(cfg->in_format, H, W));
+    s->out_bytes = align_up(packed_bytes(cfg->out_format, H, W));
     s->ws_bytes = wsb;
-    DeviceGuard g(s->device);
-    if (g.rc) { delete s; return g.rc; }
+    DeviceGuard g(cfg->device);
     const int64_t dev_total = 2 * s->in_bytes + n_t * s->out_bytes + align_up(4ll * n_t) + wsb;
     const int64_t host_total = s->in_bytes + n_t * s->out_bytes;
-    if (hipMalloc((void**)&s->mem, (size_t)dev_total) != hipSuccess) { s->mem = nullptr; release(s); return FLDR_VIDEO_E_DEVICE; }
-    if (hipHostMalloc((void**)&s->pinned, (size_t)host_total, hipHostMallocDefault) != hipSuccess) { s->pinned = nullptr; release(s); return FLDR_VIDEO_E_DEVICE; }
-    if (hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking) != hipSuccess) { s->stream = nullptr; release(s); return FLDR_VIDEO_E_DEVICE; }
-    s->slot[0] = (uint8_t*)s->mem;
+    if (!g.ok || !open_stream_mem(s->sm, cfg->device, dev_total, host_total)) { delete s; return FLDR_VIDEO_E_DEVICE; }
+    s->slot[0] = s->sm.dev;
     s->slot[1] = s->slot[0] + s->in_bytes;
     s->out_dev = s->slot[1] + s->in_bytes;
     s->t_dev = (float*)(s->out_dev + n_t * s->out_bytes);
     s->ws = (char*)s->t_dev + align_up(4ll * n_t);
     std::vector<float> t((size_t)n_t);
     for (int k = 0; k < n_t; ++k) t[k] = cfg->t ? cfg->t[k] : (float)(k + 1) / (float)(n_t + 1);
-    hipError_t e = hipMemcpyAsync(s->t_dev, t.data(), 4ull * n_t, hipMemcpyHostToDevice, s->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->stream);
-    if (e != hipSuccess) { release(s); return (int)e; }
+    hipError_t e = hipMemcpyAsync(s->t_dev, t.data(), 4ull * n_t, hipMemcpyHostToDevice, s->sm.stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(s->sm.stream);
+    if (e != hipSuccess) { fldr_video_session_destroy(s); return (int)e; }
     *out = s;
     return 0;
 }
@@ -258,14 +168,14 @@ extern "C" FLDR_VIDEO_API int fldr_video_session_push(fldr_video_session* s, con
         if (!host_outs) return FLDR_VIDEO_E_ARG;
         for (int k = 0; k < n_t; ++k) CK(check_frame(host_outs[k], c.out_format, W));
     }
-    DeviceGuard g(s->device);
-    if (g.rc) return g.rc;
+    DeviceGuard g(s->sm.device);
+    if (!g.ok) return FLDR_VIDEO_E_DEVICE;
+    const hipStream_t stream = s->sm.stream;
     const int cur = s->prev == 0 ? 1 : 0;                          // the slot not holding the previous frame
-    copy_planes(packed(s->pinned, c.in_format, H, W), *frame, c.in_format, H, W);
-    hipError_t e = hipMemcpyAsync(s->slot[cur], s->pinned, (size_t)s->in_bytes, hipMemcpyHostToDevice, s->stream);
+    hipError_t e = upload_frame(s->sm, s->slot[cur], s->sm.pinned, s->in_bytes, *frame, c.in_format, H, W);
     int rc = e == hipSuccess ? 0 : (int)e;
     const bool interp = s->prev >= 0;
-    uint8_t* out_host = s->pinned + s->in_bytes;
+    uint8_t* out_host = s->sm.pinned + s->in_bytes;
     if (!rc && interp) {
         std::vector<fldr_video_frame> outs((size_t)n_t);
         for (int k = 0; k < n_t; ++k) outs[k] = packed(s->out_dev + k * s->out_bytes, c.out_format, H, W);
@@ -277,18 +187,17 @@ extern "C" FLDR_VIDEO_API int fldr_video_session_push(fldr_video_session* s, con
         io.in[1] = packed(s->slot[cur], c.in_format, H, W);
         io.out_format = c.out_format;
         io.n_t = n_t; io.t = s->t_dev; io.out = outs.data();
-        rc = fldr_video_forward(s->model, &io, s->ws, s->ws_bytes, s->stream);
+        rc = fldr_video_forward(s->model, &io, s->ws, s->ws_bytes, stream);
         if (!rc) {
-            e = hipMemcpyAsync(out_host, s->out_dev, (size_t)(n_t * s->out_bytes), hipMemcpyDeviceToHost, s->stream);
+            e = hipMemcpyAsync(out_host, s->out_dev, (size_t)(n_t * s->out_bytes), hipMemcpyDeviceToHost, stream);
             if (e != hipSuccess) rc = (int)e;
         }
     }
-    e = hipStreamSynchronize(s->stream);
+    e = hipStreamSynchronize(stream);
     if (!rc && e != hipSuccess) rc = (int)e;
     if (rc) { s->prev = -1; return rc; }                           // the held frame is not to be trusted
     if (interp) {
-        for (int k = 0; k < n_t; ++k)
-            copy_planes(host_outs[k], packed(out_host + k * s->out_bytes, c.out_format, H, W), c.out_format, H, W);
+        for (int k = 0; k < n_t; ++k) unpack_frame(host_outs[k], out_host + k * s->out_bytes, c.out_format, H, W);
         *n_out = n_t;
     }
     s->prev = cur;
@@ -302,7 +211,7 @@ extern "C" FLDR_VIDEO_API int fldr_video_session_reset(fldr_video_session* s) {
 }
 
 extern "C" FLDR_VIDEO_API void fldr_video_session_destroy(fldr_video_session* s) {
-    if (s) release(s);
+    if (s) { close_stream_mem(s->sm); delete s; }
 }
 
 // ---- converter hooks of the test build (include/fldr_video_test_hooks.h): the two converters alone, behind fldr_video_forward's checks ---

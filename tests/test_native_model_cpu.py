@@ -12,6 +12,9 @@ import zipfile
 import numpy as np
 import pytest
 
+import lib_checks
+from lib_checks import declared as _declared
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fldr-vfi_amd")
 HDR = os.path.join(ROOT, "include", "fldr_model.h")
@@ -19,13 +22,8 @@ LIB = os.path.join(PKG, "libfldr_model.so")
 WEIGHTS = os.path.join(PKG, "weights", "fLDRnet_X4K1000FPS_exp1_best_PSNR.npz")
 
 
-def _declared(path, macro):
-    return set(re.findall(macro + r"\s+[^;(]*?\b(fldr_[a-z0-9_]+)\s*\(", open(path).read()))
-
-
 def _syms(args):
-    out = subprocess.run(["nm", "-D"] + args + [LIB], capture_output=True, text=True, check=True).stdout
-    return set(l.split()[-1] for l in out.splitlines() if l.strip())
+    return lib_checks.syms(LIB, args)
 
 
 def test_library_exports_exactly_the_header():

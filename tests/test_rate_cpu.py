@@ -16,21 +16,13 @@ import pytest
 import content_pairs as CP
 import rate_frames as RF
 import scene_oracle as S
+from lib_checks import declared as _declared, disassemble as _disassemble, syms as _syms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fldr-vfi_amd")
 INC = os.path.join(ROOT, "include")
 HDR = os.path.join(INC, "fldr_rate.h")
 LIB = os.path.join(PKG, "libfldr_rate.so")
-
-
-def _declared(path, macro):
-    return set(re.findall(macro + r"\s+[^;(]*?\b(fldr_[a-z0-9_]+)\s*\(", open(path).read()))
-
-
-def _syms(lib, args):
-    out = subprocess.run(["nm", "-D"] + args + [lib], capture_output=True, text=True, check=True).stdout
-    return set(l.split()[-1] for l in out.splitlines() if l.strip())
 
 
 # ---- the cut measure on the repository's content ----------------------------------------------------------------------------------------
@@ -194,16 +186,7 @@ def test_no_unsafe_packed_fp32_in_the_rate_library():
 
 
 def _disassembly():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import tempfile
-    import kernel_resources as KR
-    out = []
-    for blob in KR.code_objects(LIB):
-        with tempfile.NamedTemporaryFile(suffix=".co") as f:
-            f.write(blob)
-            f.flush()
-            out.append(subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", f.name], capture_output=True, text=True, check=True).stdout)
-    return "\n".join(out)
+    return "\n".join(_disassemble(LIB))
 
 
 def test_kernels_use_the_sad_instructions_and_no_ashr_pk():

@@ -15,6 +15,7 @@ import pytest
 
 import yuv_hd_oracle as HD
 import yuv_oracle as O
+from lib_checks import disassemble as _disassemble
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fldr-vfi_amd")
@@ -133,11 +134,7 @@ def _no_stale_half_packing(lib):
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_resources as KR
     n, seen = 0, False
-    for blob in KR.code_objects(lib):
-        with tempfile.NamedTemporaryFile(suffix=".co") as f:
-            f.write(blob)
-            f.flush()
-            txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", f.name], capture_output=True, text=True, check=True).stdout
+    for txt in _disassemble(lib):
         seen = seen or ("yuv420_to_planar_pair10_kernel" in txt and "planar_to_yuv420_10_kernel" in txt)
         n += len(re.findall(r"\bv_ashr_pk_\w+|\bv_cvt_pk_[ui]16_\w+", txt))
     assert seen and n == 0

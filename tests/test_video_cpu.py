@@ -13,6 +13,7 @@ import pytest
 
 import yuv_float_ref as F
 import yuv_oracle as O
+from lib_checks import declared as _declared, disassemble as _disassemble, syms as _syms
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "fldr-vfi_amd")
@@ -22,15 +23,6 @@ LIB = os.path.join(PKG, "libfldr_video.so")
 TEST_LIB = os.path.join(PKG, "libfldr_video_test.so")                          # -DFLDR_TEST_HOOKS: + include/fldr_video_test_hooks.h
 HOOKS_HDR = os.path.join(INC, "fldr_video_test_hooks.h")
 COLOR_H = os.path.join(PKG, "video", "yuv_color.h")
-
-
-def _declared(path, macro):
-    return set(re.findall(macro + r"\s+[^;(]*?\b(fldr_[a-z0-9_]+)\s*\(", open(path).read()))
-
-
-def _syms(lib, args):
-    out = subprocess.run(["nm", "-D"] + args + [lib], capture_output=True, text=True, check=True).stdout
-    return set(l.split()[-1] for l in out.splitlines() if l.strip())
 
 
 # ---- the library ----------------------------------------------------------------------------------------------------------------
@@ -93,15 +85,8 @@ def _no_unsafe_packed_fp32(lib):
 
 
 def _no_ashr_pk(lib):
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import tempfile
-    import kernel_resources as KR
     n = 0
-    for blob in KR.code_objects(lib):
-        with tempfile.NamedTemporaryFile(suffix=".co") as f:
-            f.write(blob)
-            f.flush()
-            txt = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-objdump", "-d", f.name], capture_output=True, text=True, check=True).stdout
+    for txt in _disassemble(lib):
         assert "yuv420_to_planar_pair_kernel" in txt
         n += len(re.findall(r"\bv_ashr_pk_[ui]8_i32\b", txt))
     assert n == 0
@@ -164,7 +149,7 @@ def test_no_ashr_pk_in_the_video_test_library():
 def test_hook_sources_stay_out_of_the_product_build():
     """Everything the test build adds sits behind FLDR_TEST_HOOKS: with the macro undefined the preprocessor drops every line that names
     a hook, so libfldr_video.so is compiled from the text it was compiled from before the hooks existed."""
-    for name in ("video_host.hip", "video_kernels.hip", "video_internal.h"):
+    for name in ("video_host.hip", "video_kernels.hip", "video_internal.h", "frame_host.h"):
         depth, live = [], []
         for line in open(os.path.join(PKG, "video", name)).read().splitlines():
             t = line.strip()
