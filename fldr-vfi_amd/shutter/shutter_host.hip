@@ -1,7 +1,8 @@
-// libfldr_shutter.so, host side: validation, accumulate / resolve / mix, fldr_shutter_forward (fldr_video_forward -> mix), the window rule
-// (fldr_shutter_plan) and the shutter converter for streams of host frames.  The video API's rules for formats and frames, and the
-// stream / device block / pinned block the converter owns, come from ../video/frame_host.h.  The only fldr_* functions called are those
-// of fldr_rate.h, fldr_video.h and fldr_model.h.
+// libfldr_shutter.so, host side: validation, accumulate / resolve / mix, fldr_shutter_forward (fldr_video_forward -> mix), and the public
+// face of the window rule (fldr_shutter_plan) and of the shutter converter for streams of host frames.  The rule and the converter
+// themselves are in session_host.h (shared with libfldr_light.so), which this file hands its three integration calls; the video API's
+// rules for formats and frames, and the stream / device block / pinned block the converter owns, come from ../video/frame_host.h.  The
+// only fldr_* functions called are those of fldr_rate.h, fldr_video.h and fldr_model.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -9,13 +10,12 @@
 #include <vector>
 
 #include "../video/frame_host.h"
+#include "session_host.h"
 #include "shutter_internal.h"
 
 using namespace fldr_shutter_impl;
 
 namespace {
-
-typedef __int128 wide;                 // the window rule's products: exact whatever j is
 
 bool same_format(const fldr_video_format& a, const fldr_video_format& b) {
     return a.layout == b.layout && a.matrix == b.matrix && a.range == b.range && deep(a) == deep(b);
@@ -90,44 +90,42 @@ int enqueue_mix(const Geometry& g, const fldr_video_frame* frames, const int32_t
     return launch_mix(g, src, t, vs && vt, s);
 }
 
-int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
-
-// the reduced terms of a configuration's window rule
-struct Rule {
-    int64_t A, B;                      // output j at input position j A / B
-    int64_t sn, sd;                    // the shutter
-    int64_t sub;
-    int max_out;
-};
-
-int rule_of(const fldr_shutter_config& c, Rule& r) {
-    if (c.sub < 1 || c.sub > FLDR_SHUTTER_MAX_SUB) return FLDR_SHUTTER_E_ARG;
-    if (c.in_num <= 0 || c.in_den <= 0 || c.out_num <= 0 || c.out_den <= 0 || c.shutter_num <= 0 || c.shutter_den <= 0) return FLDR_SHUTTER_E_RATIO;
-    if (c.shutter_num > c.shutter_den) return FLDR_SHUTTER_E_RATIO;
-    r.A = (int64_t)c.in_num * c.out_den; r.B = (int64_t)c.in_den * c.out_num;
-    const int64_t g = gcd64(r.A, r.B);
-    r.A /= g; r.B /= g;
-    const int64_t gs = gcd64(c.shutter_num, c.shutter_den);
-    r.sn = c.shutter_num / gs; r.sd = c.shutter_den / gs;
-    r.sub = c.sub;
-    if (r.A > (1ll << 24) || r.B > (1ll << 24) || r.sd > (1ll << 24)) return FLDR_SHUTTER_E_RATIO;
-    const wide len_n = (wide)r.sn * r.A * r.sub, len_d = (wide)r.sd * r.B;      // the window's length in grid points
-    if (len_n < len_d) return FLDR_SHUTTER_E_RATIO;                              // it could hold no point
-    if ((len_n + len_d - 1) / len_d > FLDR_SHUTTER_MAX_TOTAL) return FLDR_SHUTTER_E_RATIO;
-    const int64_t per_push = (r.B + r.A - 1) / r.A + 1;
-    if (per_push > FLDR_SHUTTER_MAX_OUT) return FLDR_SHUTTER_E_RATIO;
-    r.max_out = (int)per_push;
-    return 0;
+// the three calls as the converter of session_host.h takes them
+int op_check(void*, int H, int W, const fldr_video_format& fmt) {
+    Geometry g;
+    return geometry(H, W, fmt, g) ? 0 : FLDR_SHUTTER_E_ARG;
 }
 
-wide ceil_div(wide a, wide b) { return (a + b - 1) / b; }
-
-// m belongs to j iff j A sub sd <= m B sd < j A sub sd + sn A sub
-void window(const Rule& r, int64_t j, int64_t& first, int64_t& last) {
-    const wide lo = (wide)j * r.A * r.sub * r.sd, hi = lo + (wide)r.sn * r.A * r.sub, step = (wide)r.B * r.sd;
-    first = (int64_t)ceil_div(lo, step);
-    last = (int64_t)(ceil_div(hi, step) - 1);
+int64_t op_acc_bytes(int H, int W, const fldr_video_format& fmt) {
+    Geometry g;
+    geometry(H, W, fmt, g);
+    return align_up(4 * g.samples);
 }
+
+int64_t op_scratch_bytes(int, int, const fldr_video_format&) { return 0; }
+
+int op_accumulate(void*, int H, int W, const fldr_video_format& fmt, const fldr_video_frame* frames, const int32_t* weights, int n, bool first,
+                  void* acc, void*, hipStream_t s) {
+    Geometry g;
+    geometry(H, W, fmt, g);
+    return enqueue_accumulate(g, frames, weights, n, first, acc, s);
+}
+
+int op_resolve(void*, int H, int W, const fldr_video_format& fmt, const void* acc, int total, const fldr_video_frame& out, void*, hipStream_t s) {
+    Geometry g;
+    geometry(H, W, fmt, g);
+    return enqueue_resolve(g, acc, total, out, s);
+}
+
+int op_mix(void*, int H, int W, const fldr_video_format& fmt, const fldr_video_frame* frames, const int32_t* weights, int n,
+           const fldr_video_frame& out, void*, hipStream_t s) {
+    Geometry g;
+    geometry(H, W, fmt, g);
+    return enqueue_mix(g, frames, weights, n, out, s);
+}
+
+const Integration INTEGER_MEAN = { nullptr, FLDR_SHUTTER_E_ARG, FLDR_SHUTTER_E_RATIO, FLDR_SHUTTER_E_DEVICE, FLDR_SHUTTER_MAX_TOTAL, false,
+                                   op_check, op_acc_bytes, op_scratch_bytes, op_accumulate, op_resolve, op_mix };
 
 }  // namespace
 
@@ -253,266 +251,43 @@ extern "C" FLDR_SHUTTER_API int fldr_shutter_forward(const fldr_model* m, const 
 extern "C" FLDR_SHUTTER_API int fldr_shutter_plan(const fldr_shutter_config* cfg, int64_t j, int64_t* first, int64_t* last) {
     if (!cfg || !first || !last || j < 0) return FLDR_SHUTTER_E_ARG;
     Rule r;
-    CK(rule_of(*cfg, r));
+    CK(rule_of(*cfg, r, FLDR_SHUTTER_E_ARG, FLDR_SHUTTER_E_RATIO, FLDR_SHUTTER_MAX_TOTAL));
     window(r, j, *first, *last);
     return 0;
 }
 
-struct fldr_shutter {
-    const fldr_model* model;
-    fldr_shutter_config cfg;
-    Rule rule;
-    Geometry geo;
-    // device: slot 0, slot 1, sub - 1 sub-frames, max_out outputs, the accumulator, t, scene state, workspace
-    // pinned: one input frame, max_out output frames, t, the scene result
-    StreamMem sm;
-    int64_t frame_bytes, ws_bytes;
-    uint8_t* slot[2];
-    uint8_t* sub_dev;
-    uint8_t* out_dev;
-    void* acc;
-    float* t_dev;
-    void* state_dev;
-    void* ws;
-    uint8_t* in_host;
-    uint8_t* out_host;
-    float* t_host;
-    fldr_scene_result* scene_host;
-    int prev;                          // slot holding the previous frame, -1 when none
-    int64_t n;                         // frames pushed since create / reset
-    int64_t cuts;                      // cuts seen: the scene of the previous frame
-    int64_t j;                         // the first output not yet returned
-    int32_t open_points, open_interp;  // of window j, what the accumulator holds (0 points: not begun)
-    int64_t open_scene;
-};
-
-namespace {
-
-void restart(fldr_shutter* s) { s->prev = -1; s->n = 0; s->cuts = 0; s->j = 0; s->open_points = s->open_interp = 0; s->open_scene = 0; }
-
-// D2H of the first `count` device outputs, one synchronisation, then into the caller's frames
-int deliver(fldr_shutter* s, int rc, int count, const fldr_video_frame* host_outs) {
-    hipError_t e;
-    if (!rc && count) {
-        e = hipMemcpyAsync(s->out_host, s->out_dev, (size_t)(count * s->frame_bytes), hipMemcpyDeviceToHost, s->sm.stream);
-        if (e != hipSuccess) rc = (int)e;
-    }
-    e = hipStreamSynchronize(s->sm.stream);
-    if (!rc && e != hipSuccess) rc = (int)e;
-    if (rc) return rc;
-    for (int k = 0; k < count; ++k) unpack_frame(host_outs[k], s->out_host + k * s->frame_bytes, s->cfg.format, s->cfg.H, s->cfg.W);
-    return 0;
-}
-
-}  // namespace
+struct fldr_shutter { Session s; };
 
 extern "C" FLDR_SHUTTER_API int fldr_shutter_create(const fldr_model* m, const fldr_shutter_config* cfg, fldr_shutter** out) {
     if (!cfg || !out) return FLDR_SHUTTER_E_ARG;
     *out = nullptr;
-    if (cfg->H < 2 || cfg->W < 2 || cfg->device < 0 || (unsigned)cfg->scene > 1u) return FLDR_SHUTTER_E_ARG;
-    for (int i = 0; i < 4; ++i) if (cfg->reserved[i]) return FLDR_SHUTTER_E_ARG;
-    const fldr_scene_params& sp = cfg->scene_params;
-    if (sp.sad_permille < 0 || sp.sad_permille > 1000 || sp.hist_permille < 0 || sp.hist_permille > 1000 || sp.reserved[0] || sp.reserved[1])
-        return FLDR_SHUTTER_E_ARG;
-    CK(check_format(cfg->format));
-    Rule r;
-    CK(rule_of(*cfg, r));
-    Geometry g;
-    if (!geometry(cfg->H, cfg->W, cfg->format, g)) return FLDR_SHUTTER_E_ARG;
-    if (!m) return FLDR_SHUTTER_E_ARG;
-    const int H = cfg->H, W = cfg->W;
-    const int n_sub = cfg->sub - 1;
-    const int64_t wsb = fldr_video_workspace_bytes(m, H, W, n_sub > 0 ? n_sub : 1);
-    if (wsb < 0) return (int)wsb;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device >= ndev) { (void)hipGetLastError(); return FLDR_SHUTTER_E_DEVICE; }
-    fldr_shutter* s = new (std::nothrow) fldr_shutter();
-    if (!s) return FLDR_SHUTTER_E_DEVICE;
-    s->model = m;
-    s->cfg = *cfg;
-    s->rule = r;
-    s->geo = g;
-    restart(s);
-    s->frame_bytes = align_up(packed_bytes(cfg->format, H, W));
-    s->ws_bytes = align_up(wsb);
-    const int64_t t_bytes = align_up(4ll * FLDR_SHUTTER_MAX_SUB), acc_bytes = align_up(4 * g.samples);
-    const int64_t dev_total = (2 + n_sub + r.max_out) * s->frame_bytes + acc_bytes + t_bytes + FLDR_SCENE_STATE_BYTES + s->ws_bytes;
-    const int64_t host_total = (1 + r.max_out) * s->frame_bytes + t_bytes + ALIGN;
-    if (!open_stream_mem(s->sm, cfg->device, dev_total, host_total)) { delete s; return FLDR_SHUTTER_E_DEVICE; }
-    s->slot[0] = s->sm.dev;
-    s->slot[1] = s->slot[0] + s->frame_bytes;
-    s->sub_dev = s->slot[1] + s->frame_bytes;
-    s->out_dev = s->sub_dev + n_sub * s->frame_bytes;
-    s->acc = s->out_dev + r.max_out * s->frame_bytes;
-    s->t_dev = (float*)((char*)s->acc + acc_bytes);
-    s->state_dev = (char*)s->t_dev + t_bytes;
-    s->ws = (char*)s->state_dev + FLDR_SCENE_STATE_BYTES;
-    s->in_host = s->sm.pinned;
-    s->out_host = s->in_host + s->frame_bytes;
-    s->t_host = (float*)(s->out_host + r.max_out * s->frame_bytes);
-    s->scene_host = (fldr_scene_result*)((char*)s->t_host + t_bytes);
-    *out = s;
+    fldr_shutter* h = new (std::nothrow) fldr_shutter();
+    if (!h) return FLDR_SHUTTER_E_DEVICE;
+    const int rc = session_open(&h->s, m, cfg, INTEGER_MEAN);
+    if (rc) { delete h; return rc; }
+    *out = h;
     return 0;
 }
 
-extern "C" FLDR_SHUTTER_API int fldr_shutter_max_out(const fldr_shutter* s) { return s ? s->rule.max_out : FLDR_SHUTTER_E_ARG; }
+extern "C" FLDR_SHUTTER_API int fldr_shutter_max_out(const fldr_shutter* h) { return h ? h->s.rule.max_out : FLDR_SHUTTER_E_ARG; }
 
-extern "C" FLDR_SHUTTER_API int fldr_shutter_push(fldr_shutter* s, const fldr_video_frame* frame, const fldr_video_frame* host_outs,
+extern "C" FLDR_SHUTTER_API int fldr_shutter_push(fldr_shutter* h, const fldr_video_frame* frame, const fldr_video_frame* host_outs,
                                                   fldr_shutter_info* info, int* n_out, fldr_scene_result* scene) {
-    if (!s || !frame || !n_out) return FLDR_SHUTTER_E_ARG;
-    *n_out = 0;
-    if (scene) memset(scene, 0, sizeof(*scene));
-    const fldr_shutter_config& c = s->cfg;
-    const Rule& r = s->rule;
-    const int H = c.H, W = c.W;
-    const int sub = c.sub;
-    const fldr_video_format& fmt = c.format;
-    CK(check_frame(*frame, fmt, W));
-    // the points this push supplies, and how many outputs can end in it at the most: every window begun at or before frame n
-    const bool pair = s->prev >= 0;
-    const int64_t hi = s->n * sub, lo = pair ? hi - sub + 1 : hi;
-    int possible = 0;
-    for (int64_t j = s->j; possible < r.max_out; ++j) {
-        int64_t f, l;
-        window(r, j, f, l);
-        if (f > hi) break;
-        ++possible;
-    }
-    if (possible) {
-        if (!host_outs) return FLDR_SHUTTER_E_ARG;
-        for (int k = 0; k < possible; ++k) CK(check_frame(host_outs[k], fmt, W));
-    }
-    DeviceGuard guard(s->sm.device);
-    if (!guard.ok) return FLDR_SHUTTER_E_DEVICE;
-    const hipStream_t stream = s->sm.stream;
-    const int cur = s->prev == 0 ? 1 : 0;                          // the slot not holding the previous frame
-    hipError_t e = upload_frame(s->sm, s->slot[cur], s->in_host, s->frame_bytes, *frame, fmt, H, W);
-    int rc = e == hipSuccess ? 0 : (int)e;
-    fldr_video_frame in[2] = { packed(s->slot[pair ? s->prev : cur], fmt, H, W), packed(s->slot[cur], fmt, H, W) };
-    // the cut flag of the pair, on the host before the pair is planned
-    bool cut = false;
-    if (!rc && pair && c.scene == 1) {
-        rc = fldr_scene_measure(H, W, &fmt, in, &c.scene_params, s->state_dev, stream);
-        if (!rc) {
-            e = hipMemcpyAsync(s->scene_host, s->state_dev, sizeof(fldr_scene_result), hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) rc = (int)e;
-        }
-        if (!rc) cut = s->scene_host->cut != 0;
-    }
-    if (rc) { (void)hipStreamSynchronize(stream); restart(s); return rc; }
-    // ---- the plan: per window, the weight of frame n - 1, of frame n and of each sub-frame k = 1 .. sub - 1 ----
-    struct Step { int64_t j; int w_prev, w_cur; uint8_t w_sub[FLDR_SHUTTER_MAX_SUB]; int points, interp; bool begins, ends, truncated; };
-    std::vector<Step> steps;
-    bool wanted[FLDR_SHUTTER_MAX_SUB] = { false };
-    int64_t j = s->j;
-    int open_points = s->open_points, open_interp = s->open_interp;
-    int64_t open_scene = s->open_scene;
-    while ((int)steps.size() < r.max_out) {
-        int64_t f, l;
-        window(r, j, f, l);
-        if (f > hi) break;
-        Step st;
-        memset(&st, 0, sizeof(st));
-        st.j = j;
-        st.begins = open_points == 0;
-        const int64_t from = f > lo ? f : lo, to = l < hi ? l : hi;
-        for (int64_t m = from; m <= to; ++m) {
-            const int k = pair ? (int)(m - (hi - sub)) : sub;          // 1 .. sub; sub: the pushed frame itself
-            const int64_t sc = s->cuts + ((cut && 2 * k >= sub) ? 1 : 0);
-            if (open_points + st.points == 0) open_scene = sc;        // the window's first point names its scene
-            if (sc != open_scene) { st.truncated = true; break; }
-            ++st.points;
-            if (k == sub) ++st.w_cur;
-            else if (cut) ++(2 * k < sub ? st.w_prev : st.w_cur);
-            else { ++st.w_sub[k]; ++st.interp; wanted[k] = true; }
-        }
-        st.ends = st.truncated || l <= hi;
-        open_points += st.points;
-        open_interp += st.interp;
-        st.points = open_points;
-        st.interp = open_interp;
-        steps.push_back(st);
-        if (!st.ends) break;
-        open_points = open_interp = 0;
-        ++j;
-    }
-    // ---- one forward with exactly the sub-times some window keeps ----
-    int slot_of[FLDR_SHUTTER_MAX_SUB], n_t = 0;
-    for (int k = 1; k < sub; ++k) if (wanted[k]) { slot_of[k] = n_t; s->t_host[n_t++] = (float)k / (float)sub; }
-    if (n_t) {
-        e = hipMemcpyAsync(s->t_dev, s->t_host, 4ull * n_t, hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) rc = (int)e;
-        std::vector<fldr_video_frame> subs((size_t)n_t);
-        for (int k = 0; k < n_t; ++k) subs[k] = packed(s->sub_dev + k * s->frame_bytes, fmt, H, W);
-        fldr_video_io io;
-        memset(&io, 0, sizeof(io));
-        io.H = H; io.W = W;
-        io.in_format = io.out_format = fmt;
-        io.in[0] = in[0]; io.in[1] = in[1];
-        io.n_t = n_t; io.t = s->t_dev; io.out = subs.data();
-        if (!rc) rc = fldr_video_forward(s->model, &io, s->ws, s->ws_bytes, stream);
-    }
-    // ---- the windows, in order, on the one accumulator ----
-    int count = 0;
-    for (size_t q = 0; q < steps.size() && !rc; ++q) {
-        const Step& st = steps[q];
-        fldr_video_frame frames[MAX_FRAMES];
-        int32_t weights[MAX_FRAMES];
-        int nf = 0;
-        if (st.w_prev) { frames[nf] = in[0]; weights[nf++] = st.w_prev; }
-        for (int k = 1; k < sub; ++k)
-            if (st.w_sub[k]) { frames[nf] = packed(s->sub_dev + slot_of[k] * s->frame_bytes, fmt, H, W); weights[nf++] = st.w_sub[k]; }
-        if (st.w_cur) { frames[nf] = in[1]; weights[nf++] = st.w_cur; }
-        const fldr_video_frame out = packed(s->out_dev + count * s->frame_bytes, fmt, H, W);
-        if (st.begins && st.ends) {
-            rc = enqueue_mix(s->geo, frames, weights, nf, out, stream);         // begins with a point of this push: nf >= 1
-        } else {
-            if (nf) rc = enqueue_accumulate(s->geo, frames, weights, nf, st.begins, s->acc, stream);
-            if (!rc && st.ends) rc = enqueue_resolve(s->geo, s->acc, st.points, out, stream);
-        }
-        if (st.ends) {
-            if (info) { fldr_shutter_info i = { st.j, st.points, st.interp, st.truncated ? 1 : 0, 0 }; info[count] = i; }
-            ++count;
-        }
-    }
-    rc = deliver(s, rc, count, host_outs);
-    if (rc) { restart(s); return rc; }     // the held frame and the accumulator are not to be trusted: as after a reset
-    if (pair && c.scene == 1 && scene) *scene = *s->scene_host;
-    *n_out = count;
-    s->j = j;
-    s->open_points = open_points; s->open_interp = open_interp; s->open_scene = open_scene;
-    if (cut) s->cuts += 1;
-    s->n += 1;
-    s->prev = cur;
+    if (!h || !frame || !n_out) return FLDR_SHUTTER_E_ARG;
+    return session_push(&h->s, frame, host_outs, info, n_out, scene);
+}
+
+extern "C" FLDR_SHUTTER_API int fldr_shutter_flush(fldr_shutter* h, const fldr_video_frame* host_outs, fldr_shutter_info* info, int* n_out) {
+    if (!h || !n_out) return FLDR_SHUTTER_E_ARG;
+    return session_flush(&h->s, host_outs, info, n_out);
+}
+
+extern "C" FLDR_SHUTTER_API int fldr_shutter_reset(fldr_shutter* h) {
+    if (!h) return FLDR_SHUTTER_E_ARG;
+    session_restart(&h->s);
     return 0;
 }
 
-extern "C" FLDR_SHUTTER_API int fldr_shutter_flush(fldr_shutter* s, const fldr_video_frame* host_outs, fldr_shutter_info* info, int* n_out) {
-    if (!s || !n_out) return FLDR_SHUTTER_E_ARG;
-    *n_out = 0;
-    if (s->open_points == 0) return 0;
-    if (!host_outs) return FLDR_SHUTTER_E_ARG;
-    const fldr_shutter_config& c = s->cfg;
-    CK(check_frame(host_outs[0], c.format, c.W));
-    DeviceGuard guard(s->sm.device);
-    if (!guard.ok) return FLDR_SHUTTER_E_DEVICE;
-    int rc = enqueue_resolve(s->geo, s->acc, s->open_points, packed(s->out_dev, c.format, c.H, c.W), s->sm.stream);
-    rc = deliver(s, rc, 1, host_outs);
-    if (rc) { restart(s); return rc; }
-    if (info) { fldr_shutter_info i = { s->j, s->open_points, s->open_interp, 1, 0 }; info[0] = i; }
-    s->j += 1;
-    s->open_points = s->open_interp = 0;
-    *n_out = 1;
-    return 0;
-}
-
-extern "C" FLDR_SHUTTER_API int fldr_shutter_reset(fldr_shutter* s) {
-    if (!s) return FLDR_SHUTTER_E_ARG;
-    restart(s);
-    return 0;
-}
-
-extern "C" FLDR_SHUTTER_API void fldr_shutter_destroy(fldr_shutter* s) {
-    if (s) { close_stream_mem(s->sm); delete s; }
+extern "C" FLDR_SHUTTER_API void fldr_shutter_destroy(fldr_shutter* h) {
+    if (h) { close_stream_mem(h->s.sm); delete h; }
 }
