@@ -1,0 +1,180 @@
+// The kernels of libfldr_cadence.so: the repeat measure of a frame pair (zero, reduce every tile, write the result).
+//
+// The measure is a bandwidth kernel: one pass over the two luma planes, one 64-lane wave per tile of 32 x 32 samples.  At depth 8 a
+// tile is 32 rows of 32 bytes = 64 groups of 16 bytes: one group, one 16-byte load per frame, for every lane.  At depth 10 a tile is
+// 32 rows of 64 bytes: two groups per lane.  The four waves of a workgroup take four tiles that lie side by side, so together they
+// read whole 128-byte lines of each row.  The 16-byte loads need both plane addresses and pitches 16-byte aligned (VEC); the same
+// arithmetic runs on per-sample loads otherwise, and the bytes of a row behind its last whole 16 go sample by sample in either form.
+// Per 16 bytes: v_sad_u8 on the dwords (depth 8) or v_sad_u16 on the words reduced to 8 bits (depth 10).  A tile's sum is reduced
+// inside its wave; each wave keeps the sum, the maximum key and the count of its tiles in registers, the workgroup combines its
+// waves in LDS, and one lane adds the workgroup's three words to memory with integer atomics.  For the maximum one 64-bit atomicMax
+// on (tile_sad << 32) | (0xffffffff - index) gives the lowest index among equal maxima.  Every word is an integer sum, maximum or
+// count, so the order of the atomics does not show in the result.  No float anywhere.
+//
+// A workgroup's atomics do not go to one address for the whole grid (2040 workgroups at 3840 x 2160): the state holds STATE_SLOTS
+// accumulator slots, each on a 64-byte line of its own, a workgroup adds to the slot of its number, and the result kernel's lanes
+// combine the slots.  INTEGRATION.md section 3h has the measurement of both forms.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "cadence_internal.h"
+
+namespace fldr_cadence_impl {
+
+#define RK_THREADS 256
+#define RK_WAVES (RK_THREADS / 64)
+#define RK_MAX_BLOCKS 2048       // 8 workgroups per CU of an MI355X; larger frames walk with the grid's strides
+#define RK_TILE FLDR_REPEAT_TILE
+
+struct RepeatArgs {
+    const uint8_t* y[2];
+    int64_t pitch[2];
+    int64_t row_bytes;
+    int H;
+    uint32_t tiles_x, tiles_y;   // ceil(W / 32), ceil(H / 32)
+    uint32_t tile_sad_min;
+    uint8_t* state;
+};
+
+template <int MODE> __device__ __forceinline__ uint32_t reduce8(uint32_t w) {           // a dword of samples -> y8 in each sample's low byte
+    return MODE == Y8_BYTE ? w : MODE == Y8_P010 ? ((w >> 8) & 0x00ff00ffu) : ((w >> 2) & 0x00ff00ffu);
+}
+template <int MODE> __device__ __forceinline__ int sample8(const uint8_t* p) {
+    if (MODE == Y8_BYTE) return *p;
+    const uint32_t w = *reinterpret_cast<const uint16_t*>(p);
+    return MODE == Y8_P010 ? (int)(w >> 8) : (int)((w >> 2) & 0xffu);
+}
+
+// 16 bytes at p -> four dwords; !VEC: from loads of one sample each (p is then only sample-aligned)
+template <int MODE, bool VEC> __device__ __forceinline__ void load16(const uint8_t* p, uint32_t d[4]) {
+    if (VEC) {
+        const uint4 v = *reinterpret_cast<const uint4*>(p);
+        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
+    } else if (MODE == Y8_BYTE) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+            d[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
+    } else {
+        const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) d[i] = (uint32_t)q[2 * i] | ((uint32_t)q[2 * i + 1] << 16);
+    }
+}
+
+__global__ __launch_bounds__(RK_THREADS) void repeat_zero_kernel(uint8_t* state) {
+    reinterpret_cast<uint4*>(state)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);          // 256 x 16 = FLDR_REPEAT_STATE_BYTES
+}
+
+template <int MODE, bool VEC>
+__global__ __launch_bounds__(RK_THREADS) void repeat_tiles_kernel(RepeatArgs a) {
+    constexpr int BPS = MODE == Y8_BYTE ? 1 : 2;
+    constexpr int GROUPS = BPS;                                        // 16-byte groups per lane and tile: 64 x GROUPS x 16 = 32 x 32 x BPS
+    constexpr int GROUPS_PER_ROW = 2 * BPS;
+    __shared__ unsigned long long w_sad[RK_WAVES], w_key[RK_WAVES];
+    __shared__ uint32_t w_moving[RK_WAVES];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long sum = 0, key = 0;                               // of this wave's tiles; the same in every lane
+    uint32_t moving = 0;
+    // grid: (walkers of a tile row, each four tiles wide; walkers of the tile rows).  ty, tx and the trip counts are wave-uniform.
+    for (uint32_t ty = blockIdx.y; ty < a.tiles_y; ty += gridDim.y)
+    for (uint32_t tx = blockIdx.x * RK_WAVES + wave; tx < a.tiles_x; tx += gridDim.x * RK_WAVES) {
+        const uint32_t tile = ty * a.tiles_x + tx;
+        uint32_t sad = 0;                                              // <= 255 x 16 x GROUPS
+#pragma unroll
+        for (int g = 0; g < GROUPS; ++g) {
+            const int idx = lane + 64 * g;
+            const int row = (int)ty * RK_TILE + idx / GROUPS_PER_ROW;
+            const int64_t off = (int64_t)tx * (RK_TILE * BPS) + 16 * (idx % GROUPS_PER_ROW);
+            const int64_t left = a.row_bytes - off;                    // bytes of the row from this group on
+            if (row >= a.H || left <= 0) continue;
+            const uint8_t* p0 = a.y[0] + (int64_t)row * a.pitch[0] + off;
+            const uint8_t* p1 = a.y[1] + (int64_t)row * a.pitch[1] + off;
+            if (left >= 16) {
+                uint32_t d0[4], d1[4];
+                load16<MODE, VEC>(p0, d0);
+                load16<MODE, VEC>(p1, d1);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const uint32_t u = reduce8<MODE>(d0[i]), v = reduce8<MODE>(d1[i]);
+                    sad = MODE == Y8_BYTE ? __builtin_amdgcn_sad_u8(u, v, sad) : __builtin_amdgcn_sad_u16(u, v, sad);
+                }
+            } else {                                                   // the row's tail: left / BPS samples
+                for (int b = 0; b < (int)left; b += BPS) sad += (uint32_t)abs(sample8<MODE>(p0 + b) - sample8<MODE>(p1 + b));
+            }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) sad += (uint32_t)__shfl_xor((int)sad, m, 64);      // the tile's sum, in every lane
+        sum += sad;
+        const unsigned long long k = ((unsigned long long)sad << 32) | (unsigned long long)(0xffffffffu - tile);
+        key = k > key ? k : key;
+        moving += sad >= a.tile_sad_min ? 1u : 0u;
+    }
+    if (lane == 0) { w_sad[wave] = sum; w_key[wave] = key; w_moving[wave] = moving; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int w = 1; w < RK_WAVES; ++w) {
+            sum += w_sad[w];
+            key = w_key[w] > key ? w_key[w] : key;
+            moving += w_moving[w];
+        }
+        // a wave without a tile holds key 0, below every tile's key: the low word of a key is never 0 (tile < 2^31)
+        uint8_t* slot = a.state + STATE_SLOT_BYTES * (1 + (blockIdx.y * gridDim.x + blockIdx.x) % STATE_SLOTS);
+        if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(slot + SLOT_SAD_OFFSET), sum);
+        atomicMax(reinterpret_cast<unsigned long long*>(slot + SLOT_KEY_OFFSET), key);
+        if (moving) atomicAdd(reinterpret_cast<uint32_t*>(slot + SLOT_MOVING_OFFSET), moving);
+    }
+}
+
+// one wave: lane l >= 1 takes slot l (line 0 of the state is the result), the wave combines them, lane 0 writes
+__global__ __launch_bounds__(64) void repeat_result_kernel(uint8_t* state) {
+    static_assert(STATE_SLOTS == 63 && STATE_SLOT_BYTES * (STATE_SLOTS + 1) == FLDR_REPEAT_STATE_BYTES, "one slot per lane but lane 0");
+    const int lane = threadIdx.x;
+    const uint8_t* slot = state + STATE_SLOT_BYTES * lane;
+    unsigned long long sad = lane ? *reinterpret_cast<const unsigned long long*>(slot + SLOT_SAD_OFFSET) : 0ull;
+    unsigned long long key = lane ? *reinterpret_cast<const unsigned long long*>(slot + SLOT_KEY_OFFSET) : 0ull;
+    uint32_t moving = lane ? *reinterpret_cast<const uint32_t*>(slot + SLOT_MOVING_OFFSET) : 0u;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        sad += __shfl_xor(sad, m, 64);
+        const unsigned long long k = __shfl_xor(key, m, 64);
+        key = k > key ? k : key;
+        moving += (uint32_t)__shfl_xor((int)moving, m, 64);
+    }
+    if (lane != 0) return;
+    fldr_repeat_result* r = reinterpret_cast<fldr_repeat_result*>(state);
+    r->sad = sad;
+    r->max_tile_sad = (uint32_t)(key >> 32);
+    r->max_tile = 0xffffffffu - (uint32_t)key;
+    r->moving_tiles = moving;
+    r->repeat = moving == 0u ? 1u : 0u;
+    r->reserved[0] = r->reserved[1] = 0u;
+}
+
+int repeat_measure(const void* y0, int64_t pitch0, const void* y1, int64_t pitch1, int H, int W, int mode, int tile_sad_min, void* state,
+                   hipStream_t stream) {
+    RepeatArgs a;
+    a.y[0] = (const uint8_t*)y0; a.y[1] = (const uint8_t*)y1;
+    a.pitch[0] = pitch0; a.pitch[1] = pitch1;
+    a.row_bytes = (int64_t)W * (mode == Y8_BYTE ? 1 : 2);
+    a.H = H;
+    a.tiles_x = (uint32_t)((W + RK_TILE - 1) / RK_TILE);
+    a.tiles_y = (uint32_t)((H + RK_TILE - 1) / RK_TILE);
+    a.tile_sad_min = (uint32_t)tile_sad_min;
+    a.state = (uint8_t*)state;
+    const bool vec = ((((uintptr_t)y0 | (uintptr_t)y1 | (uintptr_t)pitch0 | (uintptr_t)pitch1) & 15) == 0);
+    // every workgroup's wave 0 has a tile: blockIdx.x * RK_WAVES < tiles_x and blockIdx.y < tiles_y
+    const uint32_t bx = min((a.tiles_x + RK_WAVES - 1) / RK_WAVES, (uint32_t)RK_MAX_BLOCKS);
+    const dim3 blocks(bx, min(a.tiles_y, (uint32_t)RK_MAX_BLOCKS / bx));
+    repeat_zero_kernel<<<1, RK_THREADS, 0, stream>>>(a.state);
+#define RK_LAUNCH(M) do { if (vec) repeat_tiles_kernel<M, true><<<blocks, RK_THREADS, 0, stream>>>(a); \
+                          else repeat_tiles_kernel<M, false><<<blocks, RK_THREADS, 0, stream>>>(a); } while (0)
+    if (mode == Y8_BYTE) RK_LAUNCH(Y8_BYTE);
+    else if (mode == Y8_P010) RK_LAUNCH(Y8_P010);
+    else RK_LAUNCH(Y8_LOW10);
+#undef RK_LAUNCH
+    repeat_result_kernel<<<1, 64, 0, stream>>>(a.state);
+    return (int)hipGetLastError();
+}
+
+}  // namespace fldr_cadence_impl

@@ -1,0 +1,208 @@
+"""ctypes binding of libfldr_cadence.so (cadence API: include/fldr_cadence.h) — the repeat measure per tile of 32 x 32 luma samples, and
+the stream that drops the repeated frames of a container stream before rate conversion, on top of fldr_rate.
+
+    m = repeat_measure((f0, f1), Format("nv12"))               # -> {"sad", "max_tile_sad", "max_tile", "moving_tiles", "repeat"}
+    c = Cadence(native_model, H, W, Format("i420"), in_rate=60, out_rate=120, cycle=5, drop=3)   # 3:2 film in 60p -> 120
+    outs = c.push((y, u, v)); ...; outs = c.flush()           # c.last_report: the cycle a call completed, or None
+
+inner_rate(in_rate, cycle, drop) is the pure-Python statement of the rate the survivors are converted from.  Frames are fldr_video's:
+tuples of 2-D plane tensors (device) or numpy arrays (host).  repeat_measure enqueues on torch's current stream (and synchronises to
+read the result back unless told not to).  No fallback: a missing library raises at load.
+"""
+import ctypes
+import os
+
+import torch
+
+import fldr_model
+import fldr_rate
+import fldr_video
+from fldr_rate import RateConfig, SceneParams, _rate
+from fldr_video import Format, Frame, _stream_ptr, frame_struct
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libfldr_cadence.so")
+CADENCE_VERSION = 100             # include/fldr_cadence.h: FLDR_CADENCE_VERSION
+E_ARG, E_STATE, E_DEVICE = -600, -601, -602
+TILE = 32
+TILE_SAD_MAX = 261120
+TILE_SAD_DEFAULT = 2048
+REPEAT_STATE_BYTES = 4096
+MAX_CYCLE = 16
+RESULT_KEYS = ("sad", "max_tile_sad", "max_tile", "moving_tiles", "repeat")
+
+
+class RepeatParams(ctypes.Structure):
+    _fields_ = [("tile_sad_min", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+    def __init__(self, tile_sad_min=0):
+        super().__init__(int(tile_sad_min))
+
+
+class RepeatResult(ctypes.Structure):
+    _fields_ = [("sad", ctypes.c_uint64), ("max_tile_sad", ctypes.c_uint32), ("max_tile", ctypes.c_uint32), ("moving_tiles", ctypes.c_uint32),
+                ("repeat", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+    def as_dict(self):
+        return {k: int(getattr(self, k)) for k in RESULT_KEYS}
+
+
+class CadenceConfig(ctypes.Structure):
+    _fields_ = [("rate", RateConfig), ("cycle", ctypes.c_int32), ("drop", ctypes.c_int32), ("repeat", RepeatParams),
+                ("reserved", ctypes.c_int32 * 2)]
+
+
+class Report(ctypes.Structure):
+    _fields_ = [("first_frame", ctypes.c_int64), ("n_frames", ctypes.c_uint32), ("dropped_mask", ctypes.c_uint32),
+                ("moving_dropped", ctypes.c_uint32), ("still_kept", ctypes.c_uint32), ("cut_mask", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32), ("measure", RepeatResult * MAX_CYCLE)]
+
+    def as_dict(self):
+        n = int(self.n_frames)
+        return {"first_frame": int(self.first_frame), "n_frames": n, "dropped_mask": int(self.dropped_mask),
+                "moving_dropped": int(self.moving_dropped), "still_kept": int(self.still_kept), "cut_mask": int(self.cut_mask),
+                "measure": [self.measure[k].as_dict() for k in range(n)]}
+
+
+_SIGNATURES = {
+    "fldr_cadence_version": (ctypes.c_int, []),
+    "fldr_cadence_error_string": (ctypes.c_char_p, [ctypes.c_int]),
+    "fldr_cadence_sizeof": (ctypes.c_int, [ctypes.c_int]),
+    "fldr_repeat_measure": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(Format), ctypes.POINTER(Frame), ctypes.POINTER(RepeatParams),
+                                           ctypes.c_void_p, ctypes.c_void_p]),
+    "fldr_cadence_inner_rate": (ctypes.c_int, [ctypes.POINTER(CadenceConfig), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "fldr_cadence_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(CadenceConfig), ctypes.POINTER(ctypes.c_void_p)]),
+    "fldr_cadence_max_out": (ctypes.c_int, [ctypes.c_void_p]),
+    "fldr_cadence_push": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.POINTER(Frame), ctypes.POINTER(ctypes.c_int),
+                                         ctypes.POINTER(Report)]),
+    "fldr_cadence_flush": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(Report)]),
+    "fldr_cadence_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "fldr_cadence_destroy": (None, [ctypes.c_void_p]),
+}
+EXPORTS = tuple(_SIGNATURES)
+_lib = None
+
+
+class CadenceError(RuntimeError):
+    def __init__(self, what, code):
+        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_cadence_error_string(code).decode(), code))
+        self.code = code
+
+
+def lib():
+    """The loaded libfldr_cadence.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
+    global _lib
+    if _lib is None:
+        fldr_rate.lib()
+        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (RepeatParams, RepeatResult, CadenceConfig, Report), "fldr_cadence", CADENCE_VERSION)
+    return _lib
+
+
+def _check(code, what):
+    if code != 0:
+        raise CadenceError(what, code)
+
+
+def inner_rate(in_rate, cycle, drop):
+    """The input rate of the inner converter: in_rate x (cycle - drop) / cycle, a Fraction."""
+    return _rate(in_rate) * (int(cycle) - int(drop)) / int(cycle)
+
+
+def inner_rate_raw(in_num, in_den, cycle, drop):
+    """fldr_cadence_inner_rate -> (code, num, den); does not raise."""
+    cfg = CadenceConfig()
+    cfg.rate.in_num, cfg.rate.in_den, cfg.cycle, cfg.drop = int(in_num), int(in_den), int(cycle), int(drop)
+    n, d = ctypes.c_int32(0), ctypes.c_int32(0)
+    return lib().fldr_cadence_inner_rate(ctypes.byref(cfg), ctypes.byref(n), ctypes.byref(d)), n.value, d.value
+
+
+# ---- the repeat measure --------------------------------------------------------------------------------------------------------------
+def repeat_state(device):
+    """FLDR_REPEAT_STATE_BYTES of device memory (torch's allocations are 256-byte aligned)."""
+    return torch.empty(REPEAT_STATE_BYTES, dtype=torch.uint8, device=device)
+
+
+def read_result(state):
+    """The fldr_repeat_result at the start of a repeat state tensor (synchronising copy) -> dict; "reserved" holds the two spare words."""
+    r = RepeatResult.from_buffer_copy(state[:ctypes.sizeof(RepeatResult)].cpu().numpy().tobytes())
+    d = r.as_dict()
+    d["reserved"] = [int(v) for v in r.reserved]
+    return d
+
+
+def repeat_measure_raw(H, W, fmt, frames, params, state_ptr, stream_ptr):
+    """The raw call; returns the code without raising (tests of the error contract)."""
+    arr = (Frame * 2)(*frames) if frames is not None else None
+    return lib().fldr_repeat_measure(int(H), int(W), ctypes.byref(fmt) if fmt is not None else None, arr,
+                                     ctypes.byref(params) if params is not None else None, state_ptr, stream_ptr)
+
+
+def repeat_measure(frames, fmt, params=None, state=None, stream=None, read=True):
+    """fldr_repeat_measure of frames (I0, I1), each a tuple of device plane tensors in `fmt` (pitches from their strides); params: a
+    RepeatParams or tile_sad_min, None = the default; state: a repeat_state tensor (allocated otherwise).  Enqueues on torch's current
+    stream; -> the result dict after a synchronising read-back, or the state tensor with read=False."""
+    H, W = frames[0][0].shape
+    device = frames[0][0].device
+    if params is not None and not isinstance(params, RepeatParams):
+        params = RepeatParams(params)
+    if state is None:
+        state = repeat_state(device)
+    _check(repeat_measure_raw(H, W, fmt, [frame_struct(f) for f in frames], params, ctypes.c_void_p(state.data_ptr()), _stream_ptr(device, stream)),
+           "fldr_repeat_measure")
+    return read_result(state) if read else state
+
+
+# ---- the stream ------------------------------------------------------------------------------------------------------------------------
+def make_config(H, W, fmt, in_rate, out_rate, cycle, drop, scene=True, device=0, scene_params=None, tile_sad_min=0):
+    cfg = CadenceConfig()
+    r = cfg.rate
+    r.H, r.W, r.device, r.scene = int(H), int(W), int(device), 1 if scene else 0
+    r.format = fmt
+    i, o = _rate(in_rate), _rate(out_rate)
+    r.in_num, r.in_den, r.out_num, r.out_den = i.numerator, i.denominator, o.numerator, o.denominator
+    if scene_params is not None:
+        r.scene_params = scene_params if isinstance(scene_params, SceneParams) else SceneParams(*scene_params)
+    cfg.cycle, cfg.drop = int(cycle), int(drop)
+    cfg.repeat = tile_sad_min if isinstance(tile_sad_min, RepeatParams) else RepeatParams(tile_sad_min)
+    return cfg
+
+
+class Cadence(fldr_video.HostStream):
+    """fldr_cadence: container frames (tuples of numpy planes) pushed one by one at in_rate, of every `cycle` of which `drop` are
+    repeats; the push that completes a cycle returns the output frames at out_rate its survivors produce, flush() those of the partial
+    last cycle and the inner converter's flush."""
+
+    _destroy = staticmethod(lambda h: lib().fldr_cadence_destroy(h))
+
+    def __init__(self, native_model, H, W, fmt=None, in_rate=60, out_rate=120, cycle=5, drop=3, scene=True, params=None, tile_sad_min=0):
+        fmt = fmt or Format()
+        cfg = make_config(H, W, fmt, in_rate, out_rate, cycle, drop, scene, native_model.device.index or 0, params, tile_sad_min)
+        self._h = ctypes.c_void_p()
+        self.model = native_model                                    # the stream uses the model: keep it alive
+        _check(lib().fldr_cadence_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_cadence_create")
+        self.H, self.W, self.format, self.cycle, self.drop = int(H), int(W), fmt, int(cycle), int(drop)
+        self.max_out = lib().fldr_cadence_max_out(self._h)
+        self._stage(fmt, H, W, self.max_out)
+        self.last_report = None
+
+    def _done(self, n, rep):
+        self.last_report = rep.as_dict() if rep.n_frames else None
+        return self._taken(n)
+
+    def push(self, frame):
+        """-> the list of output frames due (tuples of numpy planes, fresh copies): empty unless the frame completes a cycle;
+        self.last_report: that cycle's report dict, else None."""
+        fr = frame_struct(frame)
+        n = ctypes.c_int(-1)
+        rep = Report()
+        _check(lib().fldr_cadence_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n), ctypes.byref(rep)), "fldr_cadence_push")
+        return self._done(n.value, rep)
+
+    def flush(self):
+        n = ctypes.c_int(-1)
+        rep = Report()
+        _check(lib().fldr_cadence_flush(self._h, self._out_structs(), ctypes.byref(n), ctypes.byref(rep)), "fldr_cadence_flush")
+        return self._done(n.value, rep)
+
+    def reset(self):
+        _check(lib().fldr_cadence_reset(self._h), "fldr_cadence_reset")
