@@ -1,13 +1,13 @@
 // libfldr_cadence.so, host side: validation, fldr_repeat_measure, and the cadence stream (container frames in, the repeats of every
 // cycle dropped, the survivors pushed into an inner fldr_rate).  The video API's rules for formats and frames, and the stream / device
-// block / pinned block the object owns, come from ../video/frame_host.h.  The only fldr_* functions called are those of fldr_rate.h,
-// fldr_video.h and fldr_model.h.
+// block / pinned block the object owns, come from ../video/frame_host.h; the inner converter's configuration rules come from
+// ../rate/rate_plan.h, which includes it.  The only fldr_* functions called are those of fldr_rate.h, fldr_video.h and fldr_model.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <new>
 
-#include "../video/frame_host.h"
+#include "../rate/rate_plan.h"
 #include "cadence_internal.h"
 
 using namespace fldr_cadence_impl;
@@ -40,11 +40,9 @@ int check_measure(int H, int W, const fldr_video_format* fmt, const fldr_video_f
 }
 
 int enqueue_measure(int H, int W, const fldr_video_format& fmt, const fldr_video_frame in[2], int tile_sad_min, void* state, hipStream_t s) {
-    const int mode = !deep(fmt) ? Y8_BYTE : fmt.layout == FLDR_VIDEO_NV12 ? Y8_P010 : Y8_LOW10;
-    return repeat_measure(in[0].plane[0], in[0].pitch[0], in[1].plane[0], in[1].pitch[0], H, W, mode, tile_sad_min, state, s);
+    return repeat_measure(in[0].plane[0], in[0].pitch[0], in[1].plane[0], in[1].pitch[0], H, W, luma_mode(deep(fmt), fmt.layout), tile_sad_min,
+                          state, s);
 }
-
-int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
 
 bool cycle_ok(const fldr_cadence_config& c) {
     return c.cycle >= 1 && c.cycle <= FLDR_CADENCE_MAX_CYCLE && c.drop >= 0 && c.drop < c.cycle;
@@ -54,8 +52,7 @@ bool cycle_ok(const fldr_cadence_config& c) {
 int inner_rate(const fldr_cadence_config& c, int32_t& num, int32_t& den) {
     if (c.rate.in_num <= 0 || c.rate.in_den <= 0) return FLDR_RATE_E_RATIO;
     int64_t n = (int64_t)c.rate.in_num * (c.cycle - c.drop), d = (int64_t)c.rate.in_den * c.cycle;
-    const int64_t g = gcd64(n, d);
-    n /= g; d /= g;
+    reduce_terms(n, d);
     if (n > 0x7fffffffll || d > 0x7fffffffll) return FLDR_RATE_E_RATIO;
     num = (int32_t)n; den = (int32_t)d;
     return 0;
@@ -183,17 +180,9 @@ extern "C" FLDR_CADENCE_API int fldr_cadence_inner_rate(const fldr_cadence_confi
 extern "C" FLDR_CADENCE_API int fldr_cadence_create(const fldr_model* m, const fldr_cadence_config* ccfg, fldr_cadence** out) {
     if (!ccfg || !out) return FLDR_CADENCE_E_ARG;
     *out = nullptr;
-    // fldr_rate_create's checks, in its order and with its codes: a copy of the head of fldr_rate_create in ../rate/rate_host.hip (as
-    // ../pipe/pipe_host.hip has one), because cycle and drop must be judged between its rate terms and its ratio limits.  A rule that
-    // changes there changes here; tests/test_cadence_cpu.py pins the codes and their order.
+    // fldr_rate_create's checks, in its order and with its codes (../rate/rate_plan.h); cycle and drop are judged between them and its ratio limits
     const fldr_rate_config* cfg = &ccfg->rate;
-    if (cfg->H < 2 || cfg->W < 2 || cfg->device < 0 || (unsigned)cfg->scene > 1u) return FLDR_RATE_E_ARG;
-    for (int i = 0; i < 4; ++i) if (cfg->reserved[i]) return FLDR_RATE_E_ARG;
-    const fldr_scene_params& sp = cfg->scene_params;
-    if (sp.sad_permille < 0 || sp.sad_permille > 1000 || sp.hist_permille < 0 || sp.hist_permille > 1000) return FLDR_RATE_E_ARG;
-    if (sp.reserved[0] || sp.reserved[1]) return FLDR_RATE_E_ARG;
-    CK(check_format(cfg->format));
-    if (cfg->in_num <= 0 || cfg->in_den <= 0 || cfg->out_num <= 0 || cfg->out_den <= 0) return FLDR_RATE_E_RATIO;
+    CK(check_rate_config(*cfg));
     // this library's
     if (!cycle_ok(*ccfg)) return FLDR_CADENCE_E_ARG;
     int tile_sad_min;
@@ -202,10 +191,8 @@ extern "C" FLDR_CADENCE_API int fldr_cadence_create(const fldr_model* m, const f
     // the inner converter's configuration, and fldr_rate_create's limits on its ratio
     fldr_rate_config icfg = *cfg;
     CK(inner_rate(*ccfg, icfg.in_num, icfg.in_den));
-    int64_t A = (int64_t)icfg.in_num * icfg.out_den, B = (int64_t)icfg.in_den * icfg.out_num;
-    const int64_t g = gcd64(A, B);
-    A /= g; B /= g;
-    if (A > (1ll << 24) || B > (1ll << 24) || (B + A - 1) / A > FLDR_RATE_MAX_OUT) return FLDR_RATE_E_RATIO;
+    RatePlan plan;                                                     // only the limits are wanted: the inner converter makes its own
+    CK(reduce_rate(icfg.in_num, icfg.in_den, icfg.out_num, icfg.out_den, plan));
     if (!m) return FLDR_CADENCE_E_ARG;
     fldr_cadence* c = new (std::nothrow) fldr_cadence();
     if (!c) return FLDR_CADENCE_E_DEVICE;

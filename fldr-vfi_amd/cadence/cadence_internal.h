@@ -3,14 +3,11 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../rate/luma8_device.h"
 #include "fldr_cadence.h"
 
 namespace fldr_cadence_impl {
-
-// how the 8-bit luma value sits in a sample (fldr_rate.h's y8)
-enum { Y8_BYTE = 0,                    // depth 8: the byte
-       Y8_P010 = 1,                    // word >> 8
-       Y8_LOW10 = 2 };                 // (word & 0x3ff) >> 2
+using namespace fldr_luma8;
 
 // The repeat state (FLDR_REPEAT_STATE_BYTES of device memory) in lines of 64 bytes: line 0 begins with the result the caller reads,
 // lines 1 .. STATE_SLOTS are the kernels' accumulator slots; workgroup b adds to slot 1 + b % STATE_SLOTS.

@@ -36,31 +36,6 @@ struct RepeatArgs {
     uint8_t* state;
 };
 
-template <int MODE> __device__ __forceinline__ uint32_t reduce8(uint32_t w) {           // a dword of samples -> y8 in each sample's low byte
-    return MODE == Y8_BYTE ? w : MODE == Y8_P010 ? ((w >> 8) & 0x00ff00ffu) : ((w >> 2) & 0x00ff00ffu);
-}
-template <int MODE> __device__ __forceinline__ int sample8(const uint8_t* p) {
-    if (MODE == Y8_BYTE) return *p;
-    const uint32_t w = *reinterpret_cast<const uint16_t*>(p);
-    return MODE == Y8_P010 ? (int)(w >> 8) : (int)((w >> 2) & 0xffu);
-}
-
-// 16 bytes at p -> four dwords; !VEC: from loads of one sample each (p is then only sample-aligned)
-template <int MODE, bool VEC> __device__ __forceinline__ void load16(const uint8_t* p, uint32_t d[4]) {
-    if (VEC) {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    } else if (MODE == Y8_BYTE) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            d[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
-    } else {
-        const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d[i] = (uint32_t)q[2 * i] | ((uint32_t)q[2 * i + 1] << 16);
-    }
-}
-
 __global__ __launch_bounds__(RK_THREADS) void repeat_zero_kernel(uint8_t* state) {
     reinterpret_cast<uint4*>(state)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);          // 256 x 16 = FLDR_REPEAT_STATE_BYTES
 }
@@ -96,7 +71,7 @@ __global__ __launch_bounds__(RK_THREADS) void repeat_tiles_kernel(RepeatArgs a) 
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const uint32_t u = reduce8<MODE>(d0[i]), v = reduce8<MODE>(d1[i]);
-                    sad = MODE == Y8_BYTE ? __builtin_amdgcn_sad_u8(u, v, sad) : __builtin_amdgcn_sad_u16(u, v, sad);
+                    sad = sad_dword<MODE>(u, v, sad);
                 }
             } else {                                                   // the row's tail: left / BPS samples
                 for (int b = 0; b < (int)left; b += BPS) sad += (uint32_t)abs(sample8<MODE>(p0 + b) - sample8<MODE>(p1 + b));
@@ -156,23 +131,18 @@ int repeat_measure(const void* y0, int64_t pitch0, const void* y1, int64_t pitch
     RepeatArgs a;
     a.y[0] = (const uint8_t*)y0; a.y[1] = (const uint8_t*)y1;
     a.pitch[0] = pitch0; a.pitch[1] = pitch1;
-    a.row_bytes = (int64_t)W * (mode == Y8_BYTE ? 1 : 2);
+    a.row_bytes = luma_row_bytes(W, mode);
     a.H = H;
     a.tiles_x = (uint32_t)((W + RK_TILE - 1) / RK_TILE);
     a.tiles_y = (uint32_t)((H + RK_TILE - 1) / RK_TILE);
     a.tile_sad_min = (uint32_t)tile_sad_min;
     a.state = (uint8_t*)state;
-    const bool vec = ((((uintptr_t)y0 | (uintptr_t)y1 | (uintptr_t)pitch0 | (uintptr_t)pitch1) & 15) == 0);
+    const bool vec = luma_vec_ok(y0, pitch0, y1, pitch1);
     // every workgroup's wave 0 has a tile: blockIdx.x * RK_WAVES < tiles_x and blockIdx.y < tiles_y
     const uint32_t bx = min((a.tiles_x + RK_WAVES - 1) / RK_WAVES, (uint32_t)RK_MAX_BLOCKS);
     const dim3 blocks(bx, min(a.tiles_y, (uint32_t)RK_MAX_BLOCKS / bx));
     repeat_zero_kernel<<<1, RK_THREADS, 0, stream>>>(a.state);
-#define RK_LAUNCH(M) do { if (vec) repeat_tiles_kernel<M, true><<<blocks, RK_THREADS, 0, stream>>>(a); \
-                          else repeat_tiles_kernel<M, false><<<blocks, RK_THREADS, 0, stream>>>(a); } while (0)
-    if (mode == Y8_BYTE) RK_LAUNCH(Y8_BYTE);
-    else if (mode == Y8_P010) RK_LAUNCH(Y8_P010);
-    else RK_LAUNCH(Y8_LOW10);
-#undef RK_LAUNCH
+    LUMA8_LAUNCH(repeat_tiles_kernel, mode, vec, blocks, RK_THREADS, stream, a);
     repeat_result_kernel<<<1, 64, 0, stream>>>(a.state);
     return (int)hipGetLastError();
 }

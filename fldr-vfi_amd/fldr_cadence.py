@@ -17,7 +17,7 @@ import torch
 import fldr_model
 import fldr_rate
 import fldr_video
-from fldr_rate import RateConfig, SceneParams, _rate
+from fldr_rate import RateConfig, _rate, rate_config
 from fldr_video import Format, Frame, _stream_ptr, frame_struct
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -155,13 +155,7 @@ def repeat_measure(frames, fmt, params=None, state=None, stream=None, read=True)
 # ---- the stream ------------------------------------------------------------------------------------------------------------------------
 def make_config(H, W, fmt, in_rate, out_rate, cycle, drop, scene=True, device=0, scene_params=None, tile_sad_min=0):
     cfg = CadenceConfig()
-    r = cfg.rate
-    r.H, r.W, r.device, r.scene = int(H), int(W), int(device), 1 if scene else 0
-    r.format = fmt
-    i, o = _rate(in_rate), _rate(out_rate)
-    r.in_num, r.in_den, r.out_num, r.out_den = i.numerator, i.denominator, o.numerator, o.denominator
-    if scene_params is not None:
-        r.scene_params = scene_params if isinstance(scene_params, SceneParams) else SceneParams(*scene_params)
+    rate_config(H, W, fmt, in_rate, out_rate, scene, scene_params, device, into=cfg.rate)
     cfg.cycle, cfg.drop = int(cycle), int(drop)
     cfg.repeat = tile_sad_min if isinstance(tile_sad_min, RepeatParams) else RepeatParams(tile_sad_min)
     return cfg

@@ -18,7 +18,7 @@ import numpy as np
 
 import fldr_model
 import fldr_rate
-from fldr_rate import RateConfig, SceneParams, SceneResult, _rate
+from fldr_rate import RateConfig, SceneResult, rate_config
 from fldr_video import Format, Frame, frame_struct, plane_dtype, plane_shapes
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -83,13 +83,7 @@ def _check(code, what):
 def pipe_config(H, W, fmt, in_rate, out_rate, depth, scene=True, params=None, device=0):
     """A fldr_pipe_config: fldr_rate.Converter's arguments plus the depth."""
     cfg = PipeConfig()
-    r = cfg.rate
-    r.H, r.W, r.device, r.scene = int(H), int(W), int(device), 1 if scene else 0
-    r.format = fmt
-    i, o = _rate(in_rate), _rate(out_rate)
-    r.in_num, r.in_den, r.out_num, r.out_den = i.numerator, i.denominator, o.numerator, o.denominator
-    if params is not None:
-        r.scene_params = params if isinstance(params, SceneParams) else SceneParams(*params)
+    rate_config(H, W, fmt, in_rate, out_rate, scene, params, device, into=cfg.rate)
     cfg.depth = int(depth)
     return cfg
 

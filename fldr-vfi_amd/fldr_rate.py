@@ -125,6 +125,18 @@ def schedule(n_frames, in_rate, out_rate):
     return pushes
 
 
+def rate_config(H, W, fmt, in_rate, out_rate, scene=True, params=None, device=0, into=None):
+    """A fldr_rate_config from Converter's arguments; `into`: the RateConfig to fill (the `rate` member of a larger configuration)."""
+    cfg = RateConfig() if into is None else into
+    cfg.H, cfg.W, cfg.device, cfg.scene = int(H), int(W), int(device), 1 if scene else 0
+    cfg.format = fmt
+    i, o = _rate(in_rate), _rate(out_rate)
+    cfg.in_num, cfg.in_den, cfg.out_num, cfg.out_den = i.numerator, i.denominator, o.numerator, o.denominator
+    if params is not None:
+        cfg.scene_params = params if isinstance(params, SceneParams) else SceneParams(*params)
+    return cfg
+
+
 # ---- the cut measure ------------------------------------------------------------------------------------------------------------------
 def scene_state(device):
     """FLDR_SCENE_STATE_BYTES of device memory (torch's allocations are 256-byte aligned)."""
@@ -210,13 +222,7 @@ class Converter(fldr_video.HostStream):
 
     def __init__(self, native_model, H, W, fmt=None, in_rate=24, out_rate=60, scene=True, params=None):
         fmt = fmt or Format()
-        cfg = RateConfig()
-        cfg.H, cfg.W, cfg.device, cfg.scene = int(H), int(W), native_model.device.index or 0, 1 if scene else 0
-        cfg.format = fmt
-        i, o = _rate(in_rate), _rate(out_rate)
-        cfg.in_num, cfg.in_den, cfg.out_num, cfg.out_den = i.numerator, i.denominator, o.numerator, o.denominator
-        if params is not None:
-            cfg.scene_params = params if isinstance(params, SceneParams) else SceneParams(*params)
+        cfg = rate_config(H, W, fmt, in_rate, out_rate, scene, params, native_model.device.index or 0)
         self._h = ctypes.c_void_p()
         self.model = native_model                                    # the converter uses the model: keep it alive
         _check(lib().fldr_rate_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_rate_create")

@@ -1,14 +1,15 @@
 // libfldr_pipe.so: the rate converter with frames in flight (include/fldr_pipe.h).  Host code only — there is no kernel here: a job's
 // device work is fldr_rate_forward / fldr_video_forward / fldr_scene_measure, as fldr_rate_push enqueues it, between an upload on one
-// stream and a download on another.  The video API's rules for formats and frames come from ../video/frame_host.h, as in the rate
-// library.  The only fldr_* functions called are those of fldr_rate.h, fldr_video.h and fldr_model.h.
+// stream and a download on another.  The converter's configuration rules, its schedule and that device work are the text of
+// ../rate/rate_plan.h, compiled here as in the rate library; the video API's rules for formats and frames come with it from
+// ../video/frame_host.h.  The only fldr_* functions called are those of fldr_rate.h, fldr_video.h and fldr_model.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <initializer_list>
 #include <new>
 
-#include "../video/frame_host.h"
+#include "../rate/rate_plan.h"
 #include "fldr_pipe.h"
 
 namespace {
@@ -16,8 +17,6 @@ namespace {
 constexpr int64_t T_BYTES = 256;                       // FLDR_RATE_MAX_OUT floats
 constexpr int64_t SCENE_BYTES = 256;                   // a fldr_scene_result, on a line of its own
 static_assert(T_BYTES == 4 * FLDR_RATE_MAX_OUT && sizeof(fldr_scene_result) <= SCENE_BYTES, "per-job slots");
-
-int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
 
 struct Job {
     int count;                         // outputs
@@ -35,8 +34,7 @@ struct fldr_pipe {
     const fldr_model* model;
     fldr_rate_config cfg;
     int depth;
-    int64_t A, B;                      // output j at input position j A / B
-    int max_out;
+    RatePlan plan;
     int device;
     hipStream_t up, comp, down;
     hipEvent_t ev_up[FLDR_PIPE_MAX_DEPTH], ev_comp[FLDR_PIPE_MAX_DEPTH], ev_down[FLDR_PIPE_MAX_DEPTH];   // by job number mod depth
@@ -85,53 +83,25 @@ void close_pipe(fldr_pipe* p) {
 
 // everything a submit enqueues; the job record is complete when it is called
 int enqueue_push(fldr_pipe* p, const Job& job, int slot, int cur_dev, int cur_host, const int64_t* r_of) {
-    const fldr_rate_config& c = p->cfg;
-    const int H = c.H, W = c.W;
-    const fldr_video_format& fmt = c.format;
-    const bool pair = p->prev_dev >= 0, measure = job.scene;
     float* t_host = (float*)(p->t_host + slot * T_BYTES);
     float* t_dev = (float*)(p->t_dev + slot * T_BYTES);
     if (job.n_t) {
-        for (int k = 0, q = 0; k < job.count; ++k) if (r_of[k]) t_host[q++] = (float)r_of[k] / (float)p->B;
+        fill_times(r_of, job.count, p->plan.B, t_host);
         HIPRC(hipMemcpyAsync(t_dev, t_host, 4ull * job.n_t, hipMemcpyHostToDevice, p->up));
     }
     HIPRC(hipMemcpyAsync(p->in_dev + cur_dev * p->frame_bytes, p->in_host + cur_host * p->frame_bytes, (size_t)p->frame_bytes,
                          hipMemcpyHostToDevice, p->up));
     HIPRC(hipEventRecord(p->ev_up[slot], p->up));
     HIPRC(hipStreamWaitEvent(p->comp, p->ev_up[slot], 0));
-    if (pair && (job.n_t || measure)) {
-        fldr_video_frame in[2] = { packed(p->in_dev + p->prev_dev * p->frame_bytes, fmt, H, W),
-                                   packed(p->in_dev + cur_dev * p->frame_bytes, fmt, H, W) };
-        void* state = p->state_dev;
-        if (job.n_t) {
-            uint8_t* out_dev = p->out_dev + (int64_t)slot * p->max_out * p->frame_bytes;
-            fldr_video_frame outs[FLDR_RATE_MAX_OUT];
-            for (int k = 0; k < job.n_t; ++k) outs[k] = packed(out_dev + k * p->frame_bytes, fmt, H, W);
-            fldr_video_io io;
-            memset(&io, 0, sizeof(io));
-            io.H = H; io.W = W;
-            io.in_format = io.out_format = fmt;
-            io.in[0] = in[0]; io.in[1] = in[1];
-            io.n_t = job.n_t; io.t = t_dev; io.out = outs;
-            if (measure) {
-                const int64_t need = fldr_rate_workspace_bytes(p->model, H, W, job.n_t);
-                if (need < 0) return (int)need;
-                CK(fldr_rate_forward(p->model, &io, &c.scene_params, p->ws, p->ws_bytes, p->comp));
-                state = p->ws + need - FLDR_SCENE_STATE_BYTES;
-            } else {
-                CK(fldr_video_forward(p->model, &io, p->ws, p->ws_bytes, p->comp));
-            }
-        } else {
-            CK(fldr_scene_measure(H, W, &fmt, in, &c.scene_params, state, p->comp));       // a pair without an interpolated output
-        }
-        if (measure)
-            HIPRC(hipMemcpyAsync(p->scene_host + slot * SCENE_BYTES, state, sizeof(fldr_scene_result), hipMemcpyDeviceToHost, p->comp));
-    }
+    if (p->prev_dev >= 0 && (job.n_t || job.scene))
+        CK(enqueue_pair(p->model, p->cfg, job.n_t, p->in_dev + p->prev_dev * p->frame_bytes, p->in_dev + cur_dev * p->frame_bytes,
+                        p->out_dev + (int64_t)slot * p->plan.max_out * p->frame_bytes, p->frame_bytes, t_dev, p->ws, p->ws_bytes, p->state_dev,
+                        p->scene_host + slot * SCENE_BYTES, p->comp));
     HIPRC(hipEventRecord(p->ev_comp[slot], p->comp));
     HIPRC(hipStreamWaitEvent(p->down, p->ev_comp[slot], 0));
     if (job.n_t)
-        HIPRC(hipMemcpyAsync(p->out_host + (int64_t)job.out_set * p->max_out * p->frame_bytes,
-                             p->out_dev + (int64_t)slot * p->max_out * p->frame_bytes, (size_t)(job.n_t * p->frame_bytes),
+        HIPRC(hipMemcpyAsync(p->out_host + (int64_t)job.out_set * p->plan.max_out * p->frame_bytes,
+                             p->out_dev + (int64_t)slot * p->plan.max_out * p->frame_bytes, (size_t)(job.n_t * p->frame_bytes),
                              hipMemcpyDeviceToHost, p->down));
     HIPRC(hipEventRecord(p->ev_down[slot], p->down));
     return 0;
@@ -152,7 +122,7 @@ int wait_oldest(fldr_pipe* p, const Job*& job, int& slot) {
 // output k of a job, packed in pinned memory
 uint8_t* output_of(const fldr_pipe* p, const Job& job, int k, int& q) {
     if (job.direct >> k & 1) return p->in_host + job.in_slot * p->frame_bytes;
-    return p->out_host + ((int64_t)job.out_set * p->max_out + q++) * p->frame_bytes;
+    return p->out_host + ((int64_t)job.out_set * p->plan.max_out + q++) * p->frame_bytes;
 }
 
 void take_scene(const fldr_pipe* p, const Job& job, int slot, fldr_scene_result* scene) {
@@ -185,20 +155,12 @@ extern "C" FLDR_PIPE_API int fldr_pipe_sizeof(int which) {
 extern "C" FLDR_PIPE_API int fldr_pipe_create(const fldr_model* m, const fldr_pipe_config* pcfg, fldr_pipe** out) {
     if (!pcfg || !out) return FLDR_PIPE_E_ARG;
     *out = nullptr;
-    // fldr_rate_create's checks, in its order and with its codes
+    // fldr_rate_create's checks, in its order and with its codes: ../rate/rate_plan.h
     const fldr_rate_config* cfg = &pcfg->rate;
-    if (cfg->H < 2 || cfg->W < 2 || cfg->device < 0 || (unsigned)cfg->scene > 1u) return FLDR_RATE_E_ARG;
-    for (int i = 0; i < 4; ++i) if (cfg->reserved[i]) return FLDR_RATE_E_ARG;
-    const fldr_scene_params& sp = cfg->scene_params;
-    if (sp.sad_permille < 0 || sp.sad_permille > 1000 || sp.hist_permille < 0 || sp.hist_permille > 1000) return FLDR_RATE_E_ARG;
-    if (sp.reserved[0] || sp.reserved[1]) return FLDR_RATE_E_ARG;
-    CK(check_format(cfg->format));
-    if (cfg->in_num <= 0 || cfg->in_den <= 0 || cfg->out_num <= 0 || cfg->out_den <= 0) return FLDR_RATE_E_RATIO;
-    int64_t A = (int64_t)cfg->in_num * cfg->out_den, B = (int64_t)cfg->in_den * cfg->out_num;
-    const int64_t g = gcd64(A, B);
-    A /= g; B /= g;
-    if (A > (1ll << 24) || B > (1ll << 24) || (B + A - 1) / A > FLDR_RATE_MAX_OUT) return FLDR_RATE_E_RATIO;
-    const int max_out = (int)((B + A - 1) / A);
+    CK(check_rate_config(*cfg));
+    RatePlan plan;
+    CK(reduce_rate(cfg->in_num, cfg->in_den, cfg->out_num, cfg->out_den, plan));
+    const int max_out = plan.max_out;
     // this library's
     if (pcfg->depth < 1 || pcfg->depth > FLDR_PIPE_MAX_DEPTH) return FLDR_PIPE_E_ARG;
     for (int i = 0; i < 3; ++i) if (pcfg->reserved[i]) return FLDR_PIPE_E_ARG;
@@ -213,7 +175,7 @@ extern "C" FLDR_PIPE_API int fldr_pipe_create(const fldr_model* m, const fldr_pi
     p->model = m;
     p->cfg = *cfg;
     p->depth = D;
-    p->A = A; p->B = B; p->max_out = max_out;
+    p->plan = plan;
     p->device = cfg->device;
     p->job_seq = 0; p->in_seq = 0;
     fresh_stream(p);
@@ -242,7 +204,7 @@ extern "C" FLDR_PIPE_API int fldr_pipe_create(const fldr_model* m, const fldr_pi
     return 0;
 }
 
-extern "C" FLDR_PIPE_API int fldr_pipe_max_out(const fldr_pipe* p) { return p ? p->max_out : FLDR_PIPE_E_ARG; }
+extern "C" FLDR_PIPE_API int fldr_pipe_max_out(const fldr_pipe* p) { return p ? p->plan.max_out : FLDR_PIPE_E_ARG; }
 
 extern "C" FLDR_PIPE_API int fldr_pipe_pending(const fldr_pipe* p) { return p ? p->pending : FLDR_PIPE_E_ARG; }
 
@@ -257,18 +219,12 @@ extern "C" FLDR_PIPE_API int fldr_pipe_submit(fldr_pipe* p, const fldr_video_fra
     const fldr_rate_config& c = p->cfg;
     if (host_frame) CK(check_frame(*host_frame, c.format, c.W));
     if (p->pending >= p->depth) return FLDR_PIPE_E_FULL;
-    // the outputs of the pair (n - 1, n), by fldr_rate.h's rule: every j with (n - 1) B <= j A < n B; r = j A - (n - 1) B
     const bool pair = p->prev_dev >= 0;
     Job job;
     memset(&job, 0, sizeof(job));
     int64_t r_of[FLDR_RATE_MAX_OUT];
-    if (pair)
-        for (int64_t j = p->j; j * p->A < p->n * p->B && job.count < FLDR_RATE_MAX_OUT; ++j) {
-            r_of[job.count] = j * p->A - (p->n - 1) * p->B;
-            if (r_of[job.count]) ++job.n_t;
-            else job.direct |= 1ull << job.count;
-            ++job.count;
-        }
+    if (pair) job.count = pair_outputs(p->plan, p->n, p->j, r_of, job.n_t);
+    for (int k = 0; k < job.count; ++k) if (!r_of[k]) job.direct |= 1ull << k;
     const int slot = (int)(p->job_seq % p->depth);
     const int cur_dev = (int)(p->in_seq % p->n_in_dev), cur_host = (int)(p->in_seq % p->n_in_host);
     job.waits = true;
@@ -292,7 +248,7 @@ extern "C" FLDR_PIPE_API int fldr_pipe_flush(fldr_pipe* p) {
     if (p->pending >= p->depth) return FLDR_PIPE_E_FULL;
     Job job;
     memset(&job, 0, sizeof(job));
-    if (p->prev_host >= 0 && p->j * p->A == (p->n - 1) * p->B) {          // the output that lands exactly on the last frame: its bytes
+    if (p->prev_host >= 0 && flush_due(p->plan, p->n, p->j)) {          // the output that lands exactly on the last frame: its bytes
         job.count = 1;
         job.direct = 1;
         job.in_slot = p->prev_host;

@@ -1,14 +1,14 @@
 // libfldr_rate.so, host side: validation, fldr_scene_measure, fldr_rate_forward (measure -> fldr_video_forward -> select) and the rate
 // converter for streams of host frames.  The video API's rules for formats and frames, and the stream / device block / pinned block the
-// converter owns, come from ../video/frame_host.h.  The only fldr_* functions called are those of fldr_video.h and fldr_model.h.
+// converter owns, come from ../video/frame_host.h; the converter's configuration rules, its schedule and the device work of a pair from
+// rate_plan.h, which the pipe and cadence libraries compile too.  The only fldr_* functions called are those of fldr_video.h and fldr_model.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <new>
-#include <vector>
 
-#include "../video/frame_host.h"
 #include "rate_internal.h"
+#include "rate_plan.h"
 
 using namespace fldr_rate_impl;
 
@@ -18,13 +18,12 @@ bool same_format(const fldr_video_format& a, const fldr_video_format& b) {
     return a.layout == b.layout && a.matrix == b.matrix && a.range == b.range && deep(a) == deep(b);
 }
 
-// thresholds with the defaults filled in; FLDR_RATE_E_ARG outside 0 .. 1000 or with a reserved word set
+// thresholds with the defaults filled in; check_scene_params' code for those it refuses
 int resolve_params(const fldr_scene_params* p, int& sad_pm, int& hist_pm) {
     sad_pm = FLDR_SCENE_SAD_DEFAULT;
     hist_pm = FLDR_SCENE_HIST_DEFAULT;
     if (!p) return 0;
-    if (p->sad_permille < 0 || p->sad_permille > 1000 || p->hist_permille < 0 || p->hist_permille > 1000) return FLDR_RATE_E_ARG;
-    if (p->reserved[0] || p->reserved[1]) return FLDR_RATE_E_ARG;
+    CK(check_scene_params(*p));
     if (p->sad_permille) sad_pm = p->sad_permille;
     if (p->hist_permille) hist_pm = p->hist_permille;
     return 0;
@@ -43,8 +42,8 @@ int check_measure(int H, int W, const fldr_video_format* fmt, const fldr_video_f
 }
 
 int enqueue_measure(int H, int W, const fldr_video_format& fmt, const fldr_video_frame in[2], int sad_pm, int hist_pm, void* state, hipStream_t s) {
-    const int mode = !deep(fmt) ? Y8_BYTE : fmt.layout == FLDR_VIDEO_NV12 ? Y8_P010 : Y8_LOW10;
-    return scene_measure(in[0].plane[0], in[0].pitch[0], in[1].plane[0], in[1].pitch[0], H, W, mode, sad_pm, hist_pm, state, s);
+    return scene_measure(in[0].plane[0], in[0].pitch[0], in[1].plane[0], in[1].pitch[0], H, W, luma_mode(deep(fmt), fmt.layout), sad_pm, hist_pm,
+                         state, s);
 }
 
 }  // namespace
@@ -120,8 +119,7 @@ extern "C" FLDR_RATE_API int fldr_rate_forward(const fldr_model* m, const fldr_v
 struct fldr_rate {
     const fldr_model* model;
     fldr_rate_config cfg;
-    int64_t A, B;                      // output j at input position j A / B
-    int max_out;
+    RatePlan plan;
     // device: slot 0, slot 1, max_out outputs, t, scene state (pairs without a forward), workspace
     // pinned: two input frames (the held one and the new one), max_out output frames, t, the scene result
     StreamMem sm;
@@ -140,27 +138,13 @@ struct fldr_rate {
     int64_t j;                         // the next output frame
 };
 
-namespace {
-
-int64_t gcd64(int64_t a, int64_t b) { while (b) { const int64_t t = a % b; a = b; b = t; } return a; }
-
-}  // namespace
-
 extern "C" FLDR_RATE_API int fldr_rate_create(const fldr_model* m, const fldr_rate_config* cfg, fldr_rate** out) {
     if (!cfg || !out) return FLDR_RATE_E_ARG;
     *out = nullptr;
-    if (cfg->H < 2 || cfg->W < 2 || cfg->device < 0 || (unsigned)cfg->scene > 1u) return FLDR_RATE_E_ARG;
-    for (int i = 0; i < 4; ++i) if (cfg->reserved[i]) return FLDR_RATE_E_ARG;
-    int sad_pm, hist_pm;
-    CK(resolve_params(&cfg->scene_params, sad_pm, hist_pm));
-    CK(check_format(cfg->format));
-    if (cfg->in_num <= 0 || cfg->in_den <= 0 || cfg->out_num <= 0 || cfg->out_den <= 0) return FLDR_RATE_E_RATIO;
-    int64_t A = (int64_t)cfg->in_num * cfg->out_den, B = (int64_t)cfg->in_den * cfg->out_num;
-    const int64_t g = gcd64(A, B);
-    A /= g; B /= g;
-    // t = (float)r / (float)B is then exact in its operands, and t < 0.5f exactly where r * 2 < B
-    if (A > (1ll << 24) || B > (1ll << 24) || (B + A - 1) / A > FLDR_RATE_MAX_OUT) return FLDR_RATE_E_RATIO;
-    const int max_out = (int)((B + A - 1) / A);
+    CK(check_rate_config(*cfg));
+    RatePlan plan;
+    CK(reduce_rate(cfg->in_num, cfg->in_den, cfg->out_num, cfg->out_den, plan));
+    const int max_out = plan.max_out;
     if (!m) return FLDR_RATE_E_ARG;
     const int H = cfg->H, W = cfg->W;
     const int64_t wsb = fldr_rate_workspace_bytes(m, H, W, max_out);
@@ -171,7 +155,7 @@ extern "C" FLDR_RATE_API int fldr_rate_create(const fldr_model* m, const fldr_ra
     if (!s) return FLDR_RATE_E_DEVICE;
     s->model = m;
     s->cfg = *cfg;
-    s->A = A; s->B = B; s->max_out = max_out;
+    s->plan = plan;
     s->prev = -1; s->n = 0; s->j = 0;
     s->frame_bytes = align_up(packed_bytes(cfg->format, H, W));
     s->ws_bytes = wsb;
@@ -194,7 +178,7 @@ extern "C" FLDR_RATE_API int fldr_rate_create(const fldr_model* m, const fldr_ra
     return 0;
 }
 
-extern "C" FLDR_RATE_API int fldr_rate_max_out(const fldr_rate* s) { return s ? s->max_out : FLDR_RATE_E_ARG; }
+extern "C" FLDR_RATE_API int fldr_rate_max_out(const fldr_rate* s) { return s ? s->plan.max_out : FLDR_RATE_E_ARG; }
 
 extern "C" FLDR_RATE_API int fldr_rate_push(fldr_rate* s, const fldr_video_frame* frame, const fldr_video_frame* host_outs, int* n_out,
                                             fldr_scene_result* scene) {
@@ -205,16 +189,10 @@ extern "C" FLDR_RATE_API int fldr_rate_push(fldr_rate* s, const fldr_video_frame
     const int H = c.H, W = c.W;
     const fldr_video_format& fmt = c.format;
     CK(check_frame(*frame, fmt, W));
-    // the outputs of the pair (n - 1, n): every j with (n - 1) B <= j A < n B; r = j A - (n - 1) B
     const bool pair = s->prev >= 0;
-    int count = 0, n_t = 0;
+    int n_t = 0;
     int64_t r_of[FLDR_RATE_MAX_OUT];
-    if (pair)
-        for (int64_t j = s->j; j * s->A < s->n * s->B && count < FLDR_RATE_MAX_OUT; ++j) {
-            r_of[count] = j * s->A - (s->n - 1) * s->B;
-            if (r_of[count]) ++n_t;
-            ++count;
-        }
+    const int count = pair ? pair_outputs(s->plan, s->n, s->j, r_of, n_t) : 0;
     if (count) {
         if (!host_outs) return FLDR_RATE_E_ARG;
         for (int k = 0; k < count; ++k) CK(check_frame(host_outs[k], fmt, W));
@@ -227,37 +205,15 @@ extern "C" FLDR_RATE_API int fldr_rate_push(fldr_rate* s, const fldr_video_frame
     int rc = e == hipSuccess ? 0 : (int)e;
     const bool measure = pair && c.scene == 1;
     if (!rc && pair && (n_t || measure)) {
-        fldr_video_frame in[2] = { packed(s->slot[s->prev], fmt, H, W), packed(s->slot[cur], fmt, H, W) };
-        void* state = s->state_dev;
         if (n_t) {
-            for (int k = 0, q = 0; k < count; ++k) if (r_of[k]) s->t_host[q++] = (float)r_of[k] / (float)s->B;
+            fill_times(r_of, count, s->plan.B, s->t_host);
             e = hipMemcpyAsync(s->t_dev, s->t_host, 4ull * n_t, hipMemcpyHostToDevice, stream);
             if (e != hipSuccess) rc = (int)e;
-            std::vector<fldr_video_frame> outs((size_t)n_t);
-            for (int k = 0; k < n_t; ++k) outs[k] = packed(s->out_dev + k * s->frame_bytes, fmt, H, W);
-            fldr_video_io io;
-            memset(&io, 0, sizeof(io));
-            io.H = H; io.W = W;
-            io.in_format = io.out_format = fmt;
-            io.in[0] = in[0]; io.in[1] = in[1];
-            io.n_t = n_t; io.t = s->t_dev; io.out = outs.data();
-            if (!rc && measure) {
-                // the forward always runs; on a cut the select of fldr_rate_forward overwrites its outputs on the device
-                const int64_t need = fldr_rate_workspace_bytes(s->model, H, W, n_t);
-                rc = need < 0 ? (int)need : fldr_rate_forward(s->model, &io, &c.scene_params, s->ws, s->ws_bytes, stream);
-                state = (char*)s->ws + need - FLDR_SCENE_STATE_BYTES;
-            } else if (!rc) {
-                rc = fldr_video_forward(s->model, &io, s->ws, s->ws_bytes, stream);
-            }
-            if (!rc) {
-                e = hipMemcpyAsync(s->out_host, s->out_dev, (size_t)(n_t * s->frame_bytes), hipMemcpyDeviceToHost, stream);
-                if (e != hipSuccess) rc = (int)e;
-            }
-        } else {
-            rc = fldr_scene_measure(H, W, &fmt, in, &c.scene_params, state, stream);        // a pair without an interpolated output
         }
-        if (!rc && measure) {
-            e = hipMemcpyAsync(s->scene_host, state, sizeof(fldr_scene_result), hipMemcpyDeviceToHost, stream);
+        if (!rc) rc = enqueue_pair(s->model, c, n_t, s->slot[s->prev], s->slot[cur], s->out_dev, s->frame_bytes, s->t_dev, s->ws, s->ws_bytes,
+                                   s->state_dev, s->scene_host, stream);
+        if (!rc && n_t) {
+            e = hipMemcpyAsync(s->out_host, s->out_dev, (size_t)(n_t * s->frame_bytes), hipMemcpyDeviceToHost, stream);
             if (e != hipSuccess) rc = (int)e;
         }
     }
@@ -279,7 +235,7 @@ extern "C" FLDR_RATE_API int fldr_rate_push(fldr_rate* s, const fldr_video_frame
 extern "C" FLDR_RATE_API int fldr_rate_flush(fldr_rate* s, const fldr_video_frame* host_outs, int* n_out) {
     if (!s || !n_out) return FLDR_RATE_E_ARG;
     *n_out = 0;
-    if (s->prev < 0 || s->j * s->A != (s->n - 1) * s->B) return 0;
+    if (s->prev < 0 || !flush_due(s->plan, s->n, s->j)) return 0;
     if (!host_outs) return FLDR_RATE_E_ARG;
     const fldr_rate_config& c = s->cfg;
     CK(check_frame(host_outs[0], c.format, c.W));

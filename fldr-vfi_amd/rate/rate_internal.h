@@ -4,13 +4,10 @@
 #include <stdint.h>
 
 #include "fldr_rate.h"
+#include "luma8_device.h"
 
 namespace fldr_rate_impl {
-
-// how the 8-bit luma value sits in a sample
-enum { Y8_BYTE = 0,                    // depth 8: the byte
-       Y8_P010 = 1,                    // word >> 8
-       Y8_LOW10 = 2 };                 // (word & 0x3ff) >> 2
+using namespace fldr_luma8;
 
 // The scene state (FLDR_SCENE_STATE_BYTES of device memory): the result the caller reads, then the kernels' accumulators.
 constexpr int STATE_SAD_OFFSET = 64;       // uint64: the sum of absolute differences, added to by every workgroup

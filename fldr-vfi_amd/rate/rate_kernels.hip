@@ -29,31 +29,6 @@ struct MeasureArgs {
     uint8_t* state;
 };
 
-template <int MODE> __device__ __forceinline__ uint32_t reduce8(uint32_t w) {           // a dword of samples -> y8 in each sample's low byte
-    return MODE == Y8_BYTE ? w : MODE == Y8_P010 ? ((w >> 8) & 0x00ff00ffu) : ((w >> 2) & 0x00ff00ffu);
-}
-template <int MODE> __device__ __forceinline__ int sample8(const uint8_t* p) {
-    if (MODE == Y8_BYTE) return *p;
-    const uint32_t w = *reinterpret_cast<const uint16_t*>(p);
-    return MODE == Y8_P010 ? (int)(w >> 8) : (int)((w >> 2) & 0xffu);
-}
-
-// 16 bytes at p -> four dwords; !VEC: from loads of one sample each (p is then only sample-aligned)
-template <int MODE, bool VEC> __device__ __forceinline__ void load16(const uint8_t* p, uint32_t d[4]) {
-    if (VEC) {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    } else if (MODE == Y8_BYTE) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            d[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
-    } else {
-        const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d[i] = (uint32_t)q[2 * i] | ((uint32_t)q[2 * i + 1] << 16);
-    }
-}
-
 // sign x (the samples of four reduced dwords) into the wave's histogram
 template <int MODE> __device__ __forceinline__ void hist16(int* h, const uint32_t d[4], int sign) {
     constexpr int SPD = MODE == Y8_BYTE ? 4 : 2;                       // samples per dword
@@ -108,7 +83,7 @@ __global__ __launch_bounds__(SK_THREADS) void scene_accumulate_kernel(MeasureArg
             for (int i = 0; i < 4; ++i) {
                 d0[i] = reduce8<MODE>(d0[i]);
                 d1[i] = reduce8<MODE>(d1[i]);
-                sad = MODE == Y8_BYTE ? __builtin_amdgcn_sad_u8(d0[i], d1[i], sad) : __builtin_amdgcn_sad_u16(d0[i], d1[i], sad);
+                sad = sad_dword<MODE>(d0[i], d1[i], sad);
                 same = same && d0[i] == d1[i];
             }
             if (!same) {                                               // equal groups add +1 and -1 to the same bins: nothing
@@ -158,19 +133,14 @@ int scene_measure(const void* y0, int64_t pitch0, const void* y1, int64_t pitch1
     MeasureArgs a;
     a.y[0] = (const uint8_t*)y0; a.y[1] = (const uint8_t*)y1;
     a.pitch[0] = pitch0; a.pitch[1] = pitch1;
-    a.row_bytes = (int64_t)W * (mode == Y8_BYTE ? 1 : 2);
+    a.row_bytes = luma_row_bytes(W, mode);
     a.chunks = (uint32_t)((a.row_bytes + 15) / 16);
     a.items = (uint32_t)H * a.chunks;
     a.state = (uint8_t*)state;
-    const bool vec = ((((uintptr_t)y0 | (uintptr_t)y1 | (uintptr_t)pitch0 | (uintptr_t)pitch1) & 15) == 0);
+    const bool vec = luma_vec_ok(y0, pitch0, y1, pitch1);
     const uint32_t blocks = min((a.items + SK_THREADS - 1) / SK_THREADS, (uint32_t)SK_MAX_BLOCKS);
     scene_zero_kernel<<<1, SK_THREADS, 0, stream>>>(a.state);
-#define SK_LAUNCH(M) do { if (vec) scene_accumulate_kernel<M, true><<<blocks, SK_THREADS, 0, stream>>>(a); \
-                          else scene_accumulate_kernel<M, false><<<blocks, SK_THREADS, 0, stream>>>(a); } while (0)
-    if (mode == Y8_BYTE) SK_LAUNCH(Y8_BYTE);
-    else if (mode == Y8_P010) SK_LAUNCH(Y8_P010);
-    else SK_LAUNCH(Y8_LOW10);
-#undef SK_LAUNCH
+    LUMA8_LAUNCH(scene_accumulate_kernel, mode, vec, blocks, SK_THREADS, stream, a);
     scene_decide_kernel<<<1, SK_THREADS, 0, stream>>>(a.state, H, W, sad_permille, hist_permille);
     return (int)hipGetLastError();
 }

@@ -1,7 +1,8 @@
 // The host side of the frame contract of include/fldr_video.h (what a valid format and a valid frame are, how large a plane is) and the
 // plumbing of a stream object (fldr_video_session, fldr_rate): a device, a stream, one device block, one pinned block, packed frames in
-// them.  Included by video_host.hip and by ../rate/rate_host.hip: libfldr_rate.so refuses exactly the frames libfldr_video.so refuses
-// because both compile this text.  Everything is in the unnamed namespace: nothing here becomes a symbol of either library.
+// them.  Included by video_host.hip, by the shutter and light libraries' host files and, through ../rate/rate_plan.h, by the rate, pipe
+// and cadence libraries': each refuses exactly the frames libfldr_video.so refuses because all compile this text.  Everything is in
+// the unnamed namespace: nothing here becomes a symbol of any library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
