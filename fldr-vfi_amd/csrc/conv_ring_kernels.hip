@@ -1347,11 +1347,11 @@ static int g_ring_consumers = 8;
 FLDR_HOOK int fldr_debug_ring_consumers(int v) { if (v == 4 || v == 8) g_ring_consumers = v; return g_ring_consumers; }
 
 template <int NMT, int TERMS, bool HAS_RES, int NC, int TW, bool RW = false>
-static int ring_launch3(SpkArgs& a, int N, int wgs_per_xcd_max, hipStream_t s) {
+static int ring_launch3(SpkArgs& a, int N, int wgs_per_xcd_max, hipStream_t s, int walk_h) {
     using Cfg = RingCfg<NMT, TW, RW>;
     static std::atomic<uint64_t> attr_done{0};
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv3x3_ring_kernel<NMT, TERMS, HAS_RES, NC, TW, false, RW>), Cfg::LDS_BYTES, attr_done)) return e;
-    if (int e = spk_fill_geometry(a, N, wgs_per_xcd_max, TW)) return e;
+    if (int e = spk_fill_geometry(a, N, wgs_per_xcd_max, TW, walk_h)) return e;
     a.spin_limit = g_ring_spin_limit;
     hipLaunchKernelGGL((conv3x3_ring_kernel<NMT, TERMS, HAS_RES, NC, TW, false, RW>), dim3(8 * a.wgs_per_xcd), dim3((NC + RING_NLOAD) * 64), Cfg::LDS_BYTES, s, a);
     FLDR_LAUNCH_RET();
@@ -1379,10 +1379,10 @@ FLDR_HOOK int fldr_debug_ring_resident(int v) { if (v == 0 || v == 1) g_ring_res
 static int g_ring_tile_width = 0;                // 0: automatic; 16 / 32: forced
 FLDR_HOOK int fldr_debug_ring_tile_width(int v) { if (v == 0 || v == 16 || v == 32) g_ring_tile_width = v; return g_ring_tile_width; }
 
-static int ring_pick_tile_width(const SpkArgs& a, int N, int wgs_per_xcd_max) {
+static int ring_pick_tile_width(const SpkArgs& a, int N, int wgs_per_xcd_max, int walk_h) {
     if (g_ring_tile_width) return g_ring_tile_width;
     const int64_t wgs = 8ll * wgs_per_xcd_max;
-    const int64_t ty = fldr_cdiv(a.H, SPK_TH);
+    const int64_t ty = fldr_cdiv(walk_h, SPK_TH);
     const int64_t u32 = (int64_t)N * fldr_cdiv(a.W, 32) * ty * a.groups, u16 = (int64_t)N * fldr_cdiv(a.W, 16) * ty * a.groups;
     if (u32 <= wgs / 2) return 32;                                       // launches that do not fill the chip either way
     const double c32 = (double)((u32 + wgs - 1) / wgs), c16 = (double)((u16 + wgs - 1) / wgs) * RING_NARROW_COST;
@@ -1390,33 +1390,33 @@ static int ring_pick_tile_width(const SpkArgs& a, int N, int wgs_per_xcd_max) {
 }
 
 template <int NMT, int TERMS, bool HAS_RES>
-static int ring_launch2(SpkArgs& a, int N, int wpx, hipStream_t s) {
+static int ring_launch2(SpkArgs& a, int N, int wpx, hipStream_t s, int walk_h) {
 #ifdef FLDR_TEST_HOOKS
     if constexpr (NMT == 1 && TERMS == 3) {
         if (g_ring_resident && a.n_chunks <= RING_RW_MAX_CHUNKS && g_ring_tile_width != 16) {
-            const int64_t units = (int64_t)N * fldr_cdiv(a.W, SPK_TW) * fldr_cdiv(a.H, SPK_TH) * a.groups;
-            if (g_ring_consumers == 4 || (g_ring_tile_width == 0 && units >= 32ll * wpx)) return ring_launch3<NMT, TERMS, HAS_RES, 4, 32, true>(a, N, wpx, s);
-            return ring_launch3<NMT, TERMS, HAS_RES, 8, 32, true>(a, N, wpx, s);
+            const int64_t units = (int64_t)N * fldr_cdiv(a.W, SPK_TW) * fldr_cdiv(walk_h, SPK_TH) * a.groups;
+            if (g_ring_consumers == 4 || (g_ring_tile_width == 0 && units >= 32ll * wpx)) return ring_launch3<NMT, TERMS, HAS_RES, 4, 32, true>(a, N, wpx, s, walk_h);
+            return ring_launch3<NMT, TERMS, HAS_RES, 8, 32, true>(a, N, wpx, s, walk_h);
         }
     }
 #endif
-    if (g_ring_consumers == 4) return ring_launch3<NMT, TERMS, HAS_RES, 4, 32>(a, N, wpx, s);
+    if (g_ring_consumers == 4) return ring_launch3<NMT, TERMS, HAS_RES, 4, 32>(a, N, wpx, s, walk_h);
     if constexpr (NMT == 1 && TERMS == 3) {
         // 16 output channels at a large resolution (dec2: 48 -> 16 at half the frame size): with one 16-channel block every MFMA
         // needs one LDS operand read when a wave owns one tile row (8 consumers), 0.83 when it owns two (4 consumers), and the
         // LDS array, not the matrix pipe, paces the kernel: 170.7 vs 151.1 us at 1152x1920 (tools/kernel_bench.py conv).
-        const int64_t units = (int64_t)N * fldr_cdiv(a.W, SPK_TW) * fldr_cdiv(a.H, SPK_TH) * a.groups;
-        if (g_ring_consumers == 8 && g_ring_tile_width == 0 && units >= 32ll * wpx) return ring_launch3<NMT, TERMS, HAS_RES, 4, 32>(a, N, wpx, s);
+        const int64_t units = (int64_t)N * fldr_cdiv(a.W, SPK_TW) * fldr_cdiv(walk_h, SPK_TH) * a.groups;
+        if (g_ring_consumers == 8 && g_ring_tile_width == 0 && units >= 32ll * wpx) return ring_launch3<NMT, TERMS, HAS_RES, 4, 32>(a, N, wpx, s, walk_h);
     }
     if constexpr (TERMS == 3) {
-        if (ring_pick_tile_width(a, N, wpx) == 16) return ring_launch3<NMT, TERMS, HAS_RES, 8, 16>(a, N, wpx, s);
+        if (ring_pick_tile_width(a, N, wpx, walk_h) == 16) return ring_launch3<NMT, TERMS, HAS_RES, 8, 16>(a, N, wpx, s, walk_h);
     }
-    return ring_launch3<NMT, TERMS, HAS_RES, 8, 32>(a, N, wpx, s);
+    return ring_launch3<NMT, TERMS, HAS_RES, 8, 32>(a, N, wpx, s, walk_h);
 }
 
 template <int NMT, int TERMS>
-static int ring_launch(SpkArgs& a, int N, int wpx, hipStream_t s) {
-    return a.residual ? ring_launch2<NMT, TERMS, true>(a, N, wpx, s) : ring_launch2<NMT, TERMS, false>(a, N, wpx, s);
+static int ring_launch(SpkArgs& a, int N, int wpx, hipStream_t s, int walk_h) {
+    return a.residual ? ring_launch2<NMT, TERMS, true>(a, N, wpx, s, walk_h) : ring_launch2<NMT, TERMS, false>(a, N, wpx, s, walk_h);
 }
 
 // The 32x32x16 kernel where it applies: 64 or 96 output channels all stored, packed output only, no residual, launches that are not
@@ -1426,11 +1426,11 @@ static int ring_launch(SpkArgs& a, int N, int wpx, hipStream_t s) {
 #endif
 static int g_ring32 = RING32_DEFAULT;
 FLDR_HOOK int fldr_debug_ring32(int v) { if (v >= 0 && v <= 2) g_ring32 = v; return g_ring32; }
-static int ring32_launch(SpkArgs& a, int N, int wgs_per_xcd_max, hipStream_t s) {
+static int ring32_launch(SpkArgs& a, int N, int wgs_per_xcd_max, hipStream_t s, int walk_h) {
     static std::atomic<uint64_t> attr_done{0};
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv3x3_ring32_kernel), Ring32Cfg::LDS_BYTES, attr_done)) return e;
     a.groups = a.cout / 32;
-    if (int e = spk_fill_geometry(a, N, wgs_per_xcd_max, SPK_TW)) return e;
+    if (int e = spk_fill_geometry(a, N, wgs_per_xcd_max, SPK_TW, walk_h)) return e;
     a.spin_limit = g_ring_spin_limit;
     hipLaunchKernelGGL(conv3x3_ring32_kernel, dim3(8 * a.wgs_per_xcd), dim3((8 + RING_NLOAD) * 64), Ring32Cfg::LDS_BYTES, s, a);
     FLDR_LAUNCH_RET();
@@ -1443,10 +1443,10 @@ static int ring32_launch(SpkArgs& a, int N, int wgs_per_xcd_max, hipStream_t s) 
 #ifndef RING32_ROUND_COST
 #define RING32_ROUND_COST 0.8
 #endif
-static bool ring32_pays(const SpkArgs& a, int N, int wgs_per_xcd_max) {
+static bool ring32_pays(const SpkArgs& a, int N, int wgs_per_xcd_max, int walk_h) {
     if (g_ring32 == 2) return true;                                       // forced (tests, kernel_bench)
     if (a.cout != 96) return false;                                      // (64 outputs: the 16x16x32 kernel's units are 32 channels already — 35.2 vs 36.5 us at 288x480)
-    const int64_t wgs = 8ll * wgs_per_xcd_max, tx32 = fldr_cdiv(a.W, 32), ty = fldr_cdiv(a.H, SPK_TH);
+    const int64_t wgs = 8ll * wgs_per_xcd_max, tx32 = fldr_cdiv(a.W, 32), ty = fldr_cdiv(walk_h, SPK_TH);
     const int64_t u48 = (int64_t)N * tx32 * ty * a.groups, u16 = (int64_t)N * fldr_cdiv(a.W, 16) * ty * a.groups, u32 = (int64_t)N * tx32 * ty * (a.cout / 32);
     if (u32 <= wgs) return false;                                        // launches that do not fill the chip either way
     const double c48 = (double)((u48 + wgs - 1) / wgs), c16 = (double)((u16 + wgs - 1) / wgs) * RING_NARROW_COST;
@@ -1454,18 +1454,19 @@ static bool ring32_pays(const SpkArgs& a, int N, int wgs_per_xcd_max) {
     return c32 < (c48 < c16 ? c48 : c16);
 }
 
-int fldr_spk_ring_dispatch(SpkArgs& a, int N, int nmt, int terms, int wgs_per_xcd_max, hipStream_t s) {
+int fldr_spk_ring_dispatch(SpkArgs& a, int N, int nmt, int terms, int wgs_per_xcd_max, hipStream_t s, int walk_h) {
+    if (walk_h <= 0 || walk_h > a.H) walk_h = a.H;                        // the rows the unit walk covers (whole tile rows of them)
     if (g_ring32 && terms == 3 && nmt >= 2 && a.w32_off && a.cout_store == a.cout && !a.residual && !a.out_f32 && a.out_spk && g_ring_consumers == 8 &&
-        g_ring_tile_width == 0 && ring32_pays(a, N, wgs_per_xcd_max))
-        return ring32_launch(a, N, wgs_per_xcd_max, s);
+        g_ring_tile_width == 0 && ring32_pays(a, N, wgs_per_xcd_max, walk_h))
+        return ring32_launch(a, N, wgs_per_xcd_max, s, walk_h);
     if (terms == 1) {
-        if (nmt == 1) return ring_launch<1, 1>(a, N, wgs_per_xcd_max, s);
-        if (nmt == 2) return ring_launch<2, 1>(a, N, wgs_per_xcd_max, s);
-        return ring_launch<3, 1>(a, N, wgs_per_xcd_max, s);
+        if (nmt == 1) return ring_launch<1, 1>(a, N, wgs_per_xcd_max, s, walk_h);
+        if (nmt == 2) return ring_launch<2, 1>(a, N, wgs_per_xcd_max, s, walk_h);
+        return ring_launch<3, 1>(a, N, wgs_per_xcd_max, s, walk_h);
     }
-    if (nmt == 1) return ring_launch<1, 3>(a, N, wgs_per_xcd_max, s);
-    if (nmt == 2) return ring_launch<2, 3>(a, N, wgs_per_xcd_max, s);
-    return ring_launch<3, 3>(a, N, wgs_per_xcd_max, s);
+    if (nmt == 1) return ring_launch<1, 3>(a, N, wgs_per_xcd_max, s, walk_h);
+    if (nmt == 2) return ring_launch<2, 3>(a, N, wgs_per_xcd_max, s, walk_h);
+    return ring_launch<3, 3>(a, N, wgs_per_xcd_max, s, walk_h);
 }
 
 // Multi-level launch: 8 x 32 tiles, 8 consumer waves; the unit geometry of spk_fill_geometry with the units of all levels.

@@ -17,6 +17,7 @@
 // s2_tap() — the weight prepack uses the same function, so any consistent order works.
 #include "common.h"
 #include <type_traits>
+#include "row_plan.h"
 
 typedef _Float16 s2_h8 __attribute__((ext_vector_type(8)));
 typedef float s2_f4 __attribute__((ext_vector_type(4)));
@@ -31,6 +32,7 @@ typedef __attribute__((address_space(3))) void* s2_lptr_t;
 #define S2_TW 32
 #define S2_IH 18                       // (TH-1)*2 + 4
 #define S2_IW 66                       // (TW-1)*2 + 4
+static_assert(S2_TH == FLDR_PLAN_TH_CONV, "row_plan.h: stride-2 tile height");
 #define S2_RP 9                        // row pairs
 #define S2_NI 10                       // ceil(RP*IW / 64) staged (row pair, column) items per lane and channel: 2 loads, 2 dword LDS writes each
 
@@ -50,6 +52,8 @@ struct S2Args {
     int32_t tiles_x, n_tiles, tiles_per_xcd;
     int32_t N, wgs_per_xcd;    // persistent kernel: samples (tiles are numbered over all samples), workgroups per XCD
     int32_t x_shift;           // persistent kernel: the tile grid starts x_shift output columns left of the image (see s2_launch_pers)
+    int32_t out_rows;          // host side: output rows the tile walk covers (<= Hout, whole tile rows; the kernels see it through n_tiles only)
+    int32_t Hin_rows;          // source rows below this one exist (<= Hin; the *_rows entry points): a row at or beyond it is zero padding and is never read
     // second problem of a pair launch (conv4x4s2_pers_spk_kernel, gridDim.y == 2): the same source and geometry, other output channels
     const float* wpack2;
     const float* bias2;
@@ -113,7 +117,7 @@ __global__ __launch_bounds__(256, 2) void conv4x4s2_split_kernel(S2Args a) {
         const int pr = e / S2_IW, x = e % S2_IW;
         const int gy0 = iy0 + 2 * pr, gy1 = gy0 + 1, gx = ix0 + x;
         const bool okx = e < S2_RP * S2_IW && gx >= 0 && gx < a.Win;
-        const bool ok0 = okx && gy0 >= 0 && gy0 < a.Hin, ok1 = okx && gy1 >= 0 && gy1 < a.Hin;
+        const bool ok0 = okx && gy0 >= 0 && gy0 < a.Hin_rows, ok1 = okx && gy1 >= 0 && gy1 < a.Hin_rows;
         vmask0 |= ok0 ? (1u << i) : 0u;
         vmask1 |= ok1 ? (1u << i) : 0u;
         g_off0[i] = ok0 ? (uint32_t)(gy0 * a.Win + gx) : 0u;
@@ -428,12 +432,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
             const int gy0 = iy0 + it_pr2[i], gy1 = gy0 + 1, gx = ix0 + it_x[i];
             // (V4: gx is a multiple of 4 and Win % 4 == 0, so a quad is inside the image or outside it as a whole)
             const bool okx = l_dw[i] >= 0 && gx >= 0 && gx < a.Win;
-            const bool ok0 = okx && gy0 >= 0 && gy0 < a.Hin, ok1 = okx && gy1 >= 0 && gy1 < a.Hin;
+            const bool ok0 = okx && gy0 >= 0 && gy0 < a.Hin_rows, ok1 = okx && gy1 >= 0 && gy1 < a.Hin_rows;
             iss_m0 |= ok0 ? (1u << i) : 0u;
             iss_m1 |= ok1 ? (1u << i) : 0u;
             const int cx = okx ? gx : 0;                                      // (lanes without an item, columns outside: any valid address)
-            voff0[i] = (uint32_t)(min(max(gy0, 0), a.Hin - 1) * a.Win + cx) * 4u;
-            voff1[i] = (uint32_t)(min(max(gy1, 0), a.Hin - 1) * a.Win + cx) * 4u;
+            voff0[i] = (uint32_t)(min(max(gy0, 0), a.Hin_rows - 1) * a.Win + cx) * 4u;
+            voff1[i] = (uint32_t)(min(max(gy1, 0), a.Hin_rows - 1) * a.Win + cx) * 4u;
         }
     };
     // request the inputs of the issue side's (tile, chunk) into `dst` and step the issue side; wave w stages channel w
@@ -768,11 +772,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 2))) voi
         for (int i = 0; i < NIT; ++i) {
             const int gy0 = iy0 + it_pr2[i], gy1 = gy0 + 1, gx = ix0 + it_x[i];
             const bool okx = l_dw[i] >= 0 && gx >= 0 && gx < a.Win;
-            const bool ok0 = okx && gy0 >= 0 && gy0 < a.Hin, ok1 = okx && gy1 >= 0 && gy1 < a.Hin;
+            const bool ok0 = okx && gy0 >= 0 && gy0 < a.Hin_rows, ok1 = okx && gy1 >= 0 && gy1 < a.Hin_rows;
             vmask[i] = (ok0 ? 0x0000FFFFu : 0u) | (ok1 ? 0xFFFF0000u : 0u);
             const int cx = okx ? gx : 0;
-            voff0[i] = (uint32_t)(min(max(gy0, 0), a.Hin - 1) * a.Win + cx) * 16u;
-            voff1[i] = (uint32_t)(min(max(gy1, 0), a.Hin - 1) * a.Win + cx) * 16u;
+            voff0[i] = (uint32_t)(min(max(gy0, 0), a.Hin_rows - 1) * a.Win + cx) * 16u;
+            voff1[i] = (uint32_t)(min(max(gy1, 0), a.Hin_rows - 1) * a.Win + cx) * 16u;
         }
     };
     // request the 8 channels of the issue side's (tile, group) and step the issue side (past the end: the last tile again)
@@ -1054,7 +1058,7 @@ __global__ __launch_bounds__((4 + S2D_NLOAD) * 64) void conv4x4s2_dma_spk_kernel
 #pragma unroll
         for (int i = 0; i < S2D_NP; ++i) {
             const int gy = iy0 + p_wr[i], gx = ix0 + p_wc[i];
-            const bool ok = gy >= 0 && gy < a.Hin && gx >= 0 && gx < a.Win;
+            const bool ok = gy >= 0 && gy < a.Hin_rows && gx >= 0 && gx < a.Win;
             voff[i] = ok ? (uint32_t)(gy * a.Win + gx) * 16u : ~0u;
         }
     };
@@ -1331,7 +1335,7 @@ static int s2_launch(S2Args& a, int N, hipStream_t s) {
     static std::atomic<uint64_t> attr_done{0};
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv4x4s2_split_kernel<MT, NMT, PT>), Cfg::LDS_BYTES, attr_done)) return e;
     a.tiles_x = fldr_cdiv(a.Wout, S2_TW);
-    const int tiles_y = fldr_cdiv(a.Hout, S2_TH);
+    const int tiles_y = fldr_cdiv(a.out_rows, S2_TH);
     a.n_tiles = a.tiles_x * tiles_y;
     a.tiles_per_xcd = (a.n_tiles + 7) / 8;
     hipLaunchKernelGGL((conv4x4s2_split_kernel<MT, NMT, PT>), dim3(8 * a.tiles_per_xcd, N), dim3(256), Cfg::LDS_BYTES, s, a);
@@ -1378,7 +1382,7 @@ static int s2_launch_pers(S2Args& a, int N, hipStream_t s, int lds_bytes) {
     // 920 MB of planes and the kernel ran at the fabric's ~6.4 TB/s; one extra, partly filled tile column pays for it.
     a.x_shift = g_s2_xshift >= 0 ? g_s2_xshift : (a.Wout >= 256 ? 15 : 0);
     a.tiles_x = fldr_cdiv(a.Wout + a.x_shift, S2_TW);
-    a.n_tiles = a.tiles_x * fldr_cdiv(a.Hout, S2_TH);
+    a.n_tiles = a.tiles_x * fldr_cdiv(a.out_rows, S2_TH);
     a.N = N;
     const int64_t total = (int64_t)N * a.n_tiles;
     if (total >= (1ll << 30)) return FLDR_E_SHAPE;
@@ -1392,8 +1396,16 @@ static int s2_launch_pers(S2Args& a, int N, hipStream_t s, int lds_bytes) {
     return v4 ? s2_launch_pers2<MT, NMT, PT, true>(a, s, lds_bytes) : s2_launch_pers2<MT, NMT, PT, false>(a, s, lds_bytes);
 }
 
+// The row limits of the *_rows entry points: out_rows (0 = all) rounded up to whole tile rows, src_rows (0 = all) as given.
+static int s2_set_rows(S2Args& a, int out_rows, int src_rows) {
+    FLDR_CHECK_ARG(out_rows >= 0 && out_rows <= a.Hout && src_rows >= 0 && src_rows <= a.Hin);
+    a.out_rows = out_rows ? min(a.Hout, fldr_cdiv(out_rows, S2_TH) * S2_TH) : a.Hout;
+    a.Hin_rows = src_rows ? src_rows : a.Hin;
+    return 0;
+}
+
 // Same descriptor as fldr_conv2d (ksize 4, stride 2; no up2 sources, no residual); d->wpack from fldr_conv_s2_prepack.
-extern "C" int fldr_conv2d_s2_split(const fldr_conv_desc* d, fldr_stream_t stream) {
+static int s2_split_run(const fldr_conv_desc* d, int out_rows, int src_rows, fldr_stream_t stream) {
     FLDR_CHECK_ARG(d && d->wpack && (d->out || d->out_spk) && d->n_src >= 1 && d->n_src <= FLDR_CONV_MAX_SRC);
     FLDR_CHECK_ARG(d->N > 0 && d->cin > 0 && d->cin <= 112 && d->cout > 0 && d->cout <= 64 && !d->residual);
     FLDR_CHECK_ARG(d->cout_store > 0 && d->cout_store <= d->cout && d->ksize == 4 && d->stride == 2);
@@ -1415,6 +1427,7 @@ extern "C" int fldr_conv2d_s2_split(const fldr_conv_desc* d, fldr_stream_t strea
     a.wpack = d->wpack; a.bias = d->bias; a.out = d->out; a.out_spk = reinterpret_cast<unsigned char*>(d->out_spk);
     a.cin = d->cin; a.cout = d->cout; a.cout_store = d->cout_store;
     a.Hin = d->Hin; a.Win = d->Win; a.Hout = d->Hout; a.Wout = d->Wout; a.relu = d->relu; a.tiles_x = 0;
+    if (int e = s2_set_rows(a, out_rows, src_rows)) return e;
     int mt, nmt;
     s2_geometry(d->cout, mt, nmt);
     hipStream_t s = fldr_s(stream);
@@ -1429,6 +1442,8 @@ extern "C" int fldr_conv2d_s2_split(const fldr_conv_desc* d, fldr_stream_t strea
     if (nmt == 1) return s2_launch<32, 1, 2>(a, d->N, s);
     return s2_launch<32, 2, 2>(a, d->N, s);
 }
+extern "C" int fldr_conv2d_s2_split(const fldr_conv_desc* d, fldr_stream_t stream) { return s2_split_run(d, 0, 0, stream); }
+extern "C" int fldr_conv2d_s2_split_rows(const fldr_conv_desc* d, int out_rows, int src_rows, fldr_stream_t stream) { return s2_split_run(d, out_rows, src_rows, stream); }
 
 // The stride-2 4x4 convolution on a split-packed source (fldr_conv2d_s2_split's arithmetic and outputs; d->src[0] = the packed
 // tensor, d->src_c[0] = cin with cin % 8 == 0, d->src_bstride[0] in BYTES (0 for N = 1); d->wpack from fldr_conv_s2_prepack).
@@ -1439,7 +1454,7 @@ static int s2_launch_pers_spk(S2Args& a, int N, hipStream_t s, int lds_bytes, in
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv4x4s2_pers_spk_kernel<MT, NMT, PT>), lds_bytes, attr_done)) return e;
     a.x_shift = 0;                                                            // (pixels are 16-byte records: every window start is aligned)
     a.tiles_x = fldr_cdiv(a.Wout, S2_TW);
-    a.n_tiles = a.tiles_x * fldr_cdiv(a.Hout, S2_TH);
+    a.n_tiles = a.tiles_x * fldr_cdiv(a.out_rows, S2_TH);
     a.N = N;
     const int64_t total = (int64_t)N * a.n_tiles;
     if (total >= (1ll << 30)) return FLDR_E_SHAPE;
@@ -1461,7 +1476,7 @@ static int s2_launch_dma_spk(S2Args& a, int N, hipStream_t s, int lds_bytes, int
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv4x4s2_dma_spk_kernel), lds_bytes, attr_done)) return e;
     a.x_shift = 0;
     a.tiles_x = fldr_cdiv(a.Wout, S2_TW);
-    a.n_tiles = a.tiles_x * fldr_cdiv(a.Hout, S2_TH);
+    a.n_tiles = a.tiles_x * fldr_cdiv(a.out_rows, S2_TH);
     a.N = N;
     const int64_t total = (int64_t)N * a.n_tiles;
     if (total >= (1ll << 30)) return FLDR_E_SHAPE;
@@ -1472,7 +1487,7 @@ static int s2_launch_dma_spk(S2Args& a, int N, hipStream_t s, int lds_bytes, int
     FLDR_LAUNCH_RET();
 }
 
-static int s2_spk_run(const fldr_conv_desc* d, const fldr_conv_desc* d2, fldr_stream_t stream) {
+static int s2_spk_run(const fldr_conv_desc* d, const fldr_conv_desc* d2, int out_rows, int src_rows, fldr_stream_t stream) {
     FLDR_CHECK_ARG(d && d->wpack && (d->out || d->out_spk) && d->n_src == 1 && d->src[0] && !d->src_up2[0] && !d->residual);
     FLDR_CHECK_ARG(d->N > 0 && d->cin > 0 && d->cin <= 64 && (d->cin & 7) == 0 && d->src_c[0] == d->cin && d->cout > 0 && d->cout <= 64);
     FLDR_CHECK_ARG(d->cout_store > 0 && d->cout_store <= d->cout && d->ksize == 4 && d->stride == 2);
@@ -1494,6 +1509,7 @@ static int s2_spk_run(const fldr_conv_desc* d, const fldr_conv_desc* d2, fldr_st
     }
     a.cin = d->cin; a.cout = d->cout; a.cout_store = d->cout_store;
     a.Hin = d->Hin; a.Win = d->Win; a.Hout = d->Hout; a.Wout = d->Wout; a.relu = d->relu; a.tiles_x = 0;
+    if (int e = s2_set_rows(a, out_rows, src_rows)) return e;
     int mt, nmt;
     s2_geometry(d->cout, mt, nmt);
     const int n_chunks = d->cin / S2_CC;
@@ -1508,11 +1524,16 @@ static int s2_spk_run(const fldr_conv_desc* d, const fldr_conv_desc* d2, fldr_st
     return FLDR_E_SHAPE;
 }
 
-extern "C" int fldr_conv2d_s2_spk(const fldr_conv_desc* d, fldr_stream_t stream) { return s2_spk_run(d, nullptr, stream); }
+extern "C" int fldr_conv2d_s2_spk(const fldr_conv_desc* d, fldr_stream_t stream) { return s2_spk_run(d, nullptr, 0, 0, stream); }
+extern "C" int fldr_conv2d_s2_spk_rows(const fldr_conv_desc* d, int out_rows, int src_rows, fldr_stream_t stream) { return s2_spk_run(d, nullptr, out_rows, src_rows, stream); }
 
 // Two stride-2 convolutions of the SAME packed source with the same geometry in ONE launch (gridDim.y = 2): the two 32-channel halves of
 // enc3 (32 -> 64; one half's 64 KB of weights per workgroup in LDS, fLDRnet.py:617) — the bits of two fldr_conv2d_s2_spk calls.
 extern "C" int fldr_conv2d_s2_spk_pair(const fldr_conv_desc* d0, const fldr_conv_desc* d1, fldr_stream_t stream) {
     FLDR_CHECK_ARG(d0 && d1);
-    return s2_spk_run(d0, d1, stream);
+    return s2_spk_run(d0, d1, 0, 0, stream);
+}
+extern "C" int fldr_conv2d_s2_spk_pair_rows(const fldr_conv_desc* d0, const fldr_conv_desc* d1, int out_rows, int src_rows, fldr_stream_t stream) {
+    FLDR_CHECK_ARG(d0 && d1);
+    return s2_spk_run(d0, d1, out_rows, src_rows, stream);
 }

@@ -687,8 +687,11 @@ static int spk_launch(SpkArgs& a, int N, hipStream_t s) {
 }
 #endif  // FLDR_TEST_HOOKS
 
-extern "C" int fldr_conv2d_spk(const fldr_spk_conv_desc* d, fldr_stream_t stream) {
-    FLDR_CHECK_ARG(d && d->wpack && (d->out_f32 || d->out_spk) && d->n_src >= 1 && d->n_src <= FLDR_CONV_MAX_SRC);
+// rows (0 = all): fldr_conv2d_spk_rows' limit; the ring pipeline walks the tile rows that hold output rows below it, every other path computes everything
+static int spk_conv_run(const fldr_spk_conv_desc* d, int rows, fldr_stream_t stream) {
+    FLDR_CHECK_ARG(d && rows >= 0 && rows <= d->H);
+    const int walk_h = rows ? rows : d->H;
+    FLDR_CHECK_ARG(d->wpack && (d->out_f32 || d->out_spk) && d->n_src >= 1 && d->n_src <= FLDR_CONV_MAX_SRC);
     FLDR_CHECK_ARG(d->N > 0 && d->cin > 0 && d->cin <= SPK_MAX_GROUPS * 8 && d->cout > 0 && d->cout <= 96);
     FLDR_CHECK_ARG(d->cout_store > 0 && d->cout_store <= d->cout && d->H > 0 && d->W > 0);
     FLDR_CHECK_ARG(!d->residual || d->out_f32 || (d->precision & 2));           // (an fp32 residual comes with the fp32 output)
@@ -727,11 +730,11 @@ extern "C" int fldr_conv2d_spk(const fldr_spk_conv_desc* d, fldr_stream_t stream
     // on sub-groups of the same weight pack instead: 3x the workgroups, a third of the weight stream each; the
     // results are the same bits (each 16-channel block accumulates independently in the same order).
     if (nmt > 1) {
-        const int64_t units = (int64_t)d->N * fldr_cdiv(d->W, SPK_TW) * fldr_cdiv(d->H, SPK_TH) * groups;
+        const int64_t units = (int64_t)d->N * fldr_cdiv(d->W, SPK_TW) * fldr_cdiv(walk_h, SPK_TH) * groups;
         if (units <= g_spk_small_units) { a.groups = (d->cout + 15) / 16; nmt = 1; }
     }
     hipStream_t s = fldr_s(stream);
-    if (g_spk_variant == 1) return fldr_spk_ring_dispatch(a, d->N, nmt, (d->precision & 1) ? 1 : 3, g_spk_wgs_per_xcd, s);
+    if (g_spk_variant == 1) return fldr_spk_ring_dispatch(a, d->N, nmt, (d->precision & 1) ? 1 : 3, g_spk_wgs_per_xcd, s, walk_h);
 #ifndef FLDR_TEST_HOOKS
     return FLDR_E_ARG;                                               // (unreachable: the variant switch is a test-build hook)
 #else
@@ -745,6 +748,8 @@ extern "C" int fldr_conv2d_spk(const fldr_spk_conv_desc* d, fldr_stream_t stream
     return spk_launch<3, 3>(a, d->N, s);
 #endif
 }
+extern "C" int fldr_conv2d_spk(const fldr_spk_conv_desc* d, fldr_stream_t stream) { return spk_conv_run(d, 0, stream); }
+extern "C" int fldr_conv2d_spk_rows(const fldr_spk_conv_desc* d, int rows, fldr_stream_t stream) { return spk_conv_run(d, rows, stream); }
 
 #ifdef FLDR_TEST_HOOKS
 // EXPERIMENT (round 6): the convolution of `d` on conv3x3_ringrow_kernel (conv_ring_kernels.hip: ring item = 32 channels x one kernel row).

@@ -25,6 +25,7 @@
 // (dec3's zero padding).  Summation order differs from conv3x3_ring_kernel's: results agree with the two-kernel path to fp32
 // accumulation rounding (tests: error vs fp64 torch, whole-model goldens).
 #include "common.h"
+#include "row_plan.h"
 
 #define D23_TH 8
 #define D23_TW 32
@@ -62,6 +63,7 @@
 #define D23_NB 3                              // pixel blocks per fetch / MFMA unit of the producer (6 blocks per wave and K-step)
 #endif
 static_assert(D23_LDS <= 160 * 1024, "dec23: LDS");
+static_assert(D23_TH == FLDR_PLAN_TH_DEC23, "row_plan.h: dec23 tile height");
 
 typedef _Float16 d23_h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 d23_h4 __attribute__((ext_vector_type(4)));
@@ -719,8 +721,8 @@ FLDR_HOOK int fldr_debug_dec23_wgs_per_xcd(int v) { if (v > 0) g_d23_wgs_max = v
 // out_u16 (with its white level) is the fourth output form; its pairs of pixels are 32-bit stores
 static int d23_launch(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
                       const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
-                      double* out_f64, float* out_f32, void* out_u8, uint16_t* out_u16, int maxval, int H_u8, int W_u8, int N, int H, int W, fldr_stream_t stream) {
-    FLDR_CHECK_ARG(dec1_spk && enc1_spk && w2pack && bias2 && w3m && bias3 && cand && cand_bstride && cand_cstride && t && N > 0 && H > 0 && W > 0);
+                      double* out_f64, float* out_f32, void* out_u8, uint16_t* out_u16, int maxval, int H_u8, int W_u8, int N, int H, int W, int rows, fldr_stream_t stream) {
+    FLDR_CHECK_ARG(dec1_spk && enc1_spk && w2pack && bias2 && w3m && bias3 && cand && cand_bstride && cand_cstride && t && N > 0 && H > 0 && W > 0 && rows >= 0 && rows <= H);
     FLDR_CHECK_ARG((out_f64 != nullptr) + (out_f32 != nullptr) + (out_u8 != nullptr) + (out_u16 != nullptr) == 1);
     if (out_u16) { FLDR_CHECK_ARG(maxval >= 1 && maxval <= 65535); out_u8 = out_u16; }
     if (out_u8) {                                                        // the cropped rounded frame: pairs of pixels are stored together
@@ -747,7 +749,8 @@ static int d23_launch(const void* dec1_spk, const void* enc1_spk, const float* w
     a.Hc = out_u8 ? H_u8 : H; a.Wc = out_u8 ? W_u8 : W;
     a.N = N; a.H = H; a.W = W;
     a.tiles_x = fldr_cdiv(W / 2, D23_TW);
-    a.per_sample = a.tiles_x * fldr_cdiv(H / 2, D23_TH);
+    // rows > 0: the tile walk stops at the tile row that holds frame row rows - 1 (16 frame rows per tile row); the tiles below are never visited
+    a.per_sample = a.tiles_x * fldr_cdiv(fldr_cdiv(rows ? rows : H, 2), D23_TH);
     if ((int64_t)a.per_sample * N > (1ll << 30)) return FLDR_E_SHAPE;
     a.total = a.per_sample * N;
     a.per_xcd = (a.total + 7) / 8;
@@ -774,7 +777,14 @@ extern "C" int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, cons
                                 const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
                                 double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, fldr_stream_t stream) {
     return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, out_f64, out_f32, out_u8, nullptr, 0,
-                      H_u8, W_u8, N, H, W, stream);
+                      H_u8, W_u8, N, H, W, 0, stream);
+}
+
+extern "C" int fldr_dec23_synth_rows(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
+                                     const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
+                                     double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, int rows, fldr_stream_t stream) {
+    return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, out_f64, out_f32, out_u8, nullptr, 0,
+                      H_u8, W_u8, N, H, W, rows, stream);
 }
 
 extern "C" int fldr_dec23_synth_u16(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
@@ -782,5 +792,13 @@ extern "C" int fldr_dec23_synth_u16(const void* dec1_spk, const void* enc1_spk, 
                                     uint16_t* out_u16, int maxval, int H_u16, int W_u16, int N, int H, int W, fldr_stream_t stream) {
     FLDR_CHECK_ARG(out_u16);
     return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, nullptr, nullptr, nullptr, out_u16, maxval,
-                      H_u16, W_u16, N, H, W, stream);
+                      H_u16, W_u16, N, H, W, 0, stream);
+}
+
+extern "C" int fldr_dec23_synth_u16_rows(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
+                                         const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
+                                         uint16_t* out_u16, int maxval, int H_u16, int W_u16, int N, int H, int W, int rows, fldr_stream_t stream) {
+    FLDR_CHECK_ARG(out_u16);
+    return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, nullptr, nullptr, nullptr, out_u16, maxval,
+                      H_u16, W_u16, N, H, W, rows, stream);
 }

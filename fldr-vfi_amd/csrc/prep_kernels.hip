@@ -27,6 +27,7 @@ struct PrepArgs {
     int phase;                     // bit 0: z0 / z1 + flow_t0 / flow_t1; bit 1: flowback_0 / _1 + im0_tot / im1_tot (3 = everything)
     int kx, ky;                    // sx == 2^-kx / sy == 2^-ky exactly (integer source-index arithmetic), else -1
     float rkx, rky;                // 2^-(kx+1), 2^-(ky+1)
+    int rows2;                     // row limit of phase 2 (<= H; fldr_prep_desc::reserved): its rows at or beyond the limit are left untouched
 };
 
 // The 16 output planes (566 MB at 4K, read back by the splats / enc1 / dec3 only after hundreds of MB of other traffic) are
@@ -167,7 +168,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PREP_WPE)))
             put(1, fldr_div_by(acc1, 3.0f, 1.0f / 3.0f));
         }
 
-        if (ph2) {
+        if (ph2 && py < a.rows2) {                                         // wave-uniform
             // backward flows (fLDRnet.py:474-475) and backward-warped frames (:478-479)
             // (the taps' low-resolution neighbourhoods through the wave's windows; a wave whose flows are too incoherent for them redoes
             // its pixels on the global path)
@@ -188,6 +189,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PREP_WPE)))
 extern "C" int fldr_level0_prep(const fldr_prep_desc* d, fldr_stream_t stream) {
     FLDR_CHECK_ARG(d && d->ws && d->flow_lo && d->I0 && d->I1 && d->t && d->flow_t0 && d->flow_t1 && d->flowback_0 && d->flowback_1);
     FLDR_CHECK_ARG(d->im0_tot && d->im1_tot && (!d->z0 == !d->z1) && d->N > 0 && d->h > 0 && d->w > 0 && d->H > 0 && d->W > 0);
+    FLDR_CHECK_ARG(d->reserved >= 0 && d->reserved <= d->H);         // rows of flowback_* / im*_tot to produce, 0 = all
     if (d->H < d->h || d->W < d->w || (int64_t)d->H * d->W * 4 >= (1ll << 32)) return FLDR_E_SHAPE;          // upsampling only (prep_sample_up2's 3x3 neighbourhood)
     PrepArgs a;
     a.flow_lo2 = reinterpret_cast<const float2*>(d->ws); a.N = d->N; a.I0 = d->I0; a.I1 = d->I1; a.i0_bstride = d->i0_bstride; a.i1_bstride = d->i1_bstride;
@@ -200,6 +202,7 @@ extern "C" int fldr_level0_prep(const fldr_prep_desc* d, fldr_stream_t stream) {
     a.r_wm1 = 1.0f / a.inv_wm1; a.r_hm1 = 1.0f / a.inv_hm1;
     a.za0 = d->z_alpha0; a.za1 = d->z_alpha1; a.withmask = d->withmask;
     a.phase = (d->phase & 3) ? (d->phase & 3) : 3;
+    a.rows2 = d->reserved ? d->reserved : d->H;
     a.kx = a.ky = -1;
     for (int k = 0; k <= 6; ++k) {                                   // (2 o + 1 stays far inside int for any plane < 4 GB)
         if (a.sx == 1.0f / (float)(1 << k)) a.kx = k;

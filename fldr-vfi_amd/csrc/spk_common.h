@@ -3,6 +3,7 @@
 // LDS-read interleave patterns.
 #pragma once
 #include "common.h"
+#include "row_plan.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -15,6 +16,7 @@ typedef __attribute__((address_space(3))) void* klptr_t;
 #define SPK_TH 8
 #define SPK_TW 32
 #define SPK_IH (SPK_TH + 2)
+static_assert(SPK_TH == FLDR_PLAN_TH_CONV, "row_plan.h: 3x3 tile height");
 #define SPK_IW (SPK_TW + 2)
 #define SPK_PLANE 5632                          // bytes per LDS plane: 340 px * 16 B rounded up to a multiple of 256
 #define SPK_IN_BYTES (4 * SPK_PLANE)
@@ -164,9 +166,10 @@ static inline int spk_right_size(int upx, int wpx_max, int groups) {
 
 // Launch geometry shared by both pipelines: tiles, (sample, tile, group) units, XCD-contiguous unit ranges, persistent
 // workgroups per XCD (a multiple of `groups`: one output group per workgroup) and the magic numbers of spk_div.
-static inline int spk_fill_geometry(SpkArgs& a, int N, int wgs_per_xcd_max, int tile_w = SPK_TW) {
+// walk_h (0 = a.H): only the tile rows that hold output rows below it are walked (fldr_conv2d_spk_rows); the tiles below are never visited.
+static inline int spk_fill_geometry(SpkArgs& a, int N, int wgs_per_xcd_max, int tile_w = SPK_TW, int walk_h = 0) {
     a.tiles_x = fldr_cdiv(a.W, tile_w);
-    a.n_tiles = a.tiles_x * fldr_cdiv(a.H, SPK_TH);
+    a.n_tiles = a.tiles_x * fldr_cdiv(walk_h > 0 && walk_h < a.H ? walk_h : a.H, SPK_TH);
     a.n_units = N * a.n_tiles * a.groups;
     a.units_per_xcd = (a.n_units + 7) / 8;
     a.units_per_xcd = (a.units_per_xcd + a.groups - 1) / a.groups * a.groups;      // whole tiles per XCD
@@ -180,6 +183,6 @@ static inline int spk_fill_geometry(SpkArgs& a, int N, int wgs_per_xcd_max, int 
 }
 
 // conv_ring_kernels.hip: the loader / consumer ring pipeline (nmt in {1,2,3}, terms in {1,3})
-int fldr_spk_ring_dispatch(SpkArgs& a, int N, int nmt, int terms, int wgs_per_xcd_max, hipStream_t s);
+int fldr_spk_ring_dispatch(SpkArgs& a, int N, int nmt, int terms, int wgs_per_xcd_max, hipStream_t s, int walk_h = 0);
 // ... for a multi-level launch (a.n_levels > 1, a.lv filled, n_units = the sum over the levels)
 int fldr_spk_ring_dispatch_levels(SpkArgs& a, int n_units, int nmt, int terms, int wgs_per_xcd_max, hipStream_t s);

@@ -18,6 +18,7 @@
 // (scattered candidates).  Queue overflow or too many super-blocks: the rectangle grows to the blocks' bounding box / the
 // image.  Every visited source is re-tested per corner, so any superset of the true candidates gives the exact result.
 #include "splat_common.h"
+#include "row_plan.h"
 
 #define SA_SBQ 64                    // matching super-blocks a workgroup can list
 #define SA_Q 512                     // matching blocks a workgroup can queue
@@ -30,6 +31,7 @@
 #define SA_IMG_K 3
 #define SA_IMG_U 4
 #endif
+static_assert(SA_IMG_TH == FLDR_PLAN_TH_SPLAT, "row_plan.h: image splat tile height");
 #ifndef SA_IMGQ_U
 #define SA_IMGQ_U 1                  // 4-pixel runs per thread in flight (QUAD walk)
 #endif
@@ -58,6 +60,7 @@ struct SaArgs {
     int whole;                                    // 1: no bounds tables, every tile walks the whole map
     int gpw;                                      // channel groups per workgroup (1 or `groups`)
     int tiles_x, st_y, n_st, total, per_xcd;      // tiles per row, super-tile rows, super-tiles per (problem, sample, group), all work items, items per XCD
+    int rows;                                     // row limit (<= H; fldr_splat_acc_desc::reserved): rows at or beyond the limit, rounded up to whole tiles, are left untouched
 };
 
 template <int CB, int U, bool QUAD>
@@ -524,7 +527,7 @@ __global__ __launch_bounds__(256) void splat_acc64_kernel(SaArgs a) {
             if (k0 + 2 * U < n_chunks) load_iter(b0, k0 + 2 * U);
             process(b1);
         }
-        const bool next = u + 1 < n_units && sy0 + ((u + 1) / a.gpw) * TH < H;
+        const bool next = u + 1 < n_units && sy0 + ((u + 1) / a.gpw) * TH < a.rows;
         if (next) begin_unit(u + 1);
         __syncthreads();
         finish(cur_y0, cur_cbase);
@@ -555,7 +558,7 @@ static int sa_launch2(SaArgs& a, int nprob, hipStream_t s) {
     static std::atomic<uint64_t> attr_done{0};
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&splat_acc64_kernel<MODE, CB, TW, TH, K, U, QUAD>), LDS, attr_done)) return e;
     a.tiles_x = fldr_cdiv(a.W, TW);
-    a.st_y = fldr_cdiv(a.H, K * TH);
+    a.st_y = fldr_cdiv(a.rows, K * TH);
     a.n_st = a.tiles_x * a.st_y;
     const int64_t total = (int64_t)nprob * a.N * (a.groups / a.gpw) * a.n_st;
     if (total > (1ll << 30)) return FLDR_E_SHAPE;
@@ -595,10 +598,12 @@ extern "C" int fldr_softsplat_acc64(const fldr_splat_acc_desc* d, fldr_stream_t 
     // flags: bit 0 tables of ws[j] already filled; bit 1 ws[0] holds the pair tables of fldr_splat_bounds_upsampled_pair (always laid
     // out for TWO problems: nprob must be 2, and bit 0 would name a different layout); bit 2 whole-map walk, no tables
     FLDR_CHECK_ARG(!(d->flags & ~7) && (!(d->flags & 2) || (d->nprob == 2 && !(d->flags & 1))));
+    FLDR_CHECK_ARG(d->reserved >= 0 && d->reserved <= d->H);         // destination rows to produce, 0 = all
     if (d->W > 65535 * ST_BW || d->H > 32767 * ST_BH || (int64_t)d->H * d->W * 4 >= (1ll << 32)) return FLDR_E_SHAPE;
     if ((int64_t)fldr_cdiv(d->W, ST_SBX * ST_BW) * fldr_cdiv(d->H, ST_SBY * ST_BH) > 65535) return FLDR_E_SHAPE;
     SaArgs a;
     a.N = d->N; a.C = d->C; a.H = d->H; a.W = d->W; a.groups = 1;
+    a.rows = d->reserved ? d->reserved : d->H;
     // maps of at most SA_WHOLE_PIXELS pixels (the coarse pyramid levels) need no tables: flags bit 2 forces that walk for any size
     a.whole = ((d->flags & 4) || (!(d->flags & 3) && (int64_t)d->H * d->W <= SA_WHOLE_PIXELS)) ? 1 : 0;
     a.nsb_x = fldr_cdiv(d->W, ST_SBX * ST_BW);

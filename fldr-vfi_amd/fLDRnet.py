@@ -37,6 +37,8 @@ def _dparam(*shape):
 
 
 class DCTXVFInet(nn.Module):
+    accepts_crop = True        # forward takes the keyword `crop` (fldr_harness.interpolate asks before it passes it: the reference's class has no such keyword)
+
     def __init__(self, args):
         super().__init__()
         self.args = args
@@ -121,13 +123,16 @@ class DCTXVFInet(nn.Module):
         y = fldr_hip.conv2d_spk([pca if pca_spk is None else pca_spk], c0.weight, c0.bias, relu=True, want_f32=False, want_spk=True)
         return fldr_hip.conv2d_spk([y], c2.weight, c2.bias, relu=True, residual=pca, want_f32=True, want_spk=True)
 
-    def forward(self, input_gpuList, t_value, normInput=0, is_training=True, validation=False, epoch=0, frameT=None, *, emit_u8=None, emit_u16=None):
+    def forward(self, input_gpuList, t_value, normInput=0, is_training=True, validation=False, epoch=0, frameT=None, *, emit_u8=None, emit_u16=None, crop=None):
         """input_gpuList: ignored placeholders (the reference overwrites them, fLDRnet.py:134); t_value [B,1];
         normInput: list of S_tst+1 tensors [B,3,2,H/2^i,W/2^i].  Returns (out fp64 [B,3,<=2160,<=4096], flow|None).
         emit_u8 = (H, W) (keyword-only, not in the reference's signature; fldr_harness.interpolate_u8): return the frame cropped to H x W and
         rounded to 8 bits straight from the synthesis kernel where the fused kernel runs (the fp64 frame is then never written); paths that
         cannot honour it return the fp64 frame as ever — the caller looks at the dtype.  emit_u16 = (H, W): the same in 16-bit words, white
-        level 1023 (10-bit code values; fldr_harness.interpolate_u16)."""
+        level 1023 (10-bit code values; fldr_harness.interpolate_u16).
+        crop = (H, W) (keyword-only): the caller only looks at the top H rows of the fp64 frame (fldr_harness.interpolate crops to the unpadded
+        frame).  The fused synthesis path then produces only the rows those need (fldr_synth_row_plan); the frame's rows below that are left
+        untouched, as are the rows beyond this function's own 2160-row crop and the rows beyond emit_u8 / emit_u16."""
         if is_training:
             raise NotImplementedError("fldr-hip implements the inference (test) branch only")
         # fault flags of EARLIER forwards, read without a synchronisation (two host words the kernels store into): a drop-in caller that
@@ -179,8 +184,9 @@ class DCTXVFInet(nn.Module):
                 feats[level] = None
             state = {"key": (x_l[0], x_l[0]._version), "flow0": flow}
             self._pair_state = state if self.pair_cache else None
+        shown = min([x_l[0].shape[3], self.output_size_test[0]] + [int(c[0]) for c in (emit_u8, emit_u16, crop) if c is not None])
         out, refined = self.vfinet._synthesise(state["flow0"], x_l[0], t4, validation,
-                                               cache=state if self.pair_cache else None, u8_crop=emit_u8, u16_crop=emit_u16)
+                                               cache=state if self.pair_cache else None, u8_crop=emit_u8, u16_crop=emit_u16, shown_rows=shown)
         return out[:, :, :self.output_size_test[0], :self.output_size_test[1]], refined                # :222
 
 
@@ -298,7 +304,7 @@ class DCTVFInet(nn.Module):
         return flow_l
 
     # ---- level 0 (fLDRnet.py:400-535) ------------------------------------------------------------
-    def _synthesise(self, flow_l, x_l, t_value, validation, cache=None, u8_crop=None, u16_crop=None):
+    def _synthesise(self, flow_l, x_l, t_value, validation, cache=None, u8_crop=None, u16_crop=None, shown_rows=None):
         a = self.args
         B = flow_l.shape[0]
         t4 = t_value.view(B, 1, 1, 1).float()
@@ -323,7 +329,18 @@ class DCTVFInet(nn.Module):
         if inv is not None:
             z0, z1 = inv
         lowres_tables = fldr_hip.SPLAT_BOUNDS == "lowres" and fldr_hip.SPLAT_KERNEL in ("auto", "acc64")
-        r = fldr_hip.level0_prep(flow_l, I0, I1, t4, H, W, za0, za1, withmask=mask, want_z=bool(a.impmasksoftsplat) and inv is None)
+        unet = self.refine_unet
+        fused = (fldr_hip.DEC23_FUSED and fldr_hip.use_spk() and fldr_hip.CONV_PRECISION == "split" and H % 4 == 0 and W % 4 == 0
+                 and tuple(unet.dec3.weight.shape) == (6, 16, 3, 3) and tuple(unet.dec2.weight.shape) == (16, 48, 3, 3))
+        # Only the top `shown_rows` rows of the frame are looked at (the 2160-row crop of DCTXVFInet.forward, the drivers' crop to the unpadded
+        # frame): on the fused default path every stage from here on produces just the rows those need (fldr_synth_row_plan: derived backwards
+        # from the crop through receptive fields and tile heights) and leaves the rest of its output untouched.  Phase 1 of the prep kernel
+        # stays whole: a source pixel in the padding can splat upwards into a needed row.
+        plan = None
+        if fused and lowres_tables and shown_rows is not None and unet.row_limits_ok():
+            plan = fldr_hip.synth_row_plan(H, shown_rows)
+        r = fldr_hip.level0_prep(flow_l, I0, I1, t4, H, W, za0, za1, withmask=mask, want_z=bool(a.impmasksoftsplat) and inv is None,
+                                 rows2=plan.prep2 if plan else None)
         if inv is None:
             z0, z1 = r["z0"], r["z1"]                                                                   # :442-446
             if cache is not None:
@@ -334,7 +351,7 @@ class DCTVFInet(nn.Module):
             # splats in one launch (fp64 LDS atomics)
             bw = fldr_hip.splat_bounds_upsampled_pair(flow_l, t4, "images", up, H, W)
             warped0, warped1 = fldr_hip.softsplat_acc64([I0, I1], [flow_t0, flow_t1], [z0, z1] if z0 is not None else None,
-                                                        self.softsplat.strType, bounds_ws=bw)          # :449-450
+                                                        self.softsplat.strType, bounds_ws=bw, rows=plan.splat if plan else None)   # :449-450
         else:
             warped0 = self.softsplat(I0, flow_t0, z=z0)                                                # :449
             warped1 = self.softsplat(I1, flow_t1, z=z1)                                                # :450
@@ -342,15 +359,13 @@ class DCTVFInet(nn.Module):
         im0_tot, im1_tot = r["im0_tot"], r["im1_tot"]                                                   # :478-479
         srcs = [I0, I1, warped0, warped1, flow_t0, flow_t1, flowback_0, flowback_1, im0_tot, im1_tot]  # :480 (no cat)
         cands = [warped0, warped1, im0_tot, im1_tot, I0, I1]
-        unet = self.refine_unet
-        if (fldr_hip.DEC23_FUSED and fldr_hip.use_spk() and fldr_hip.CONV_PRECISION == "split" and H % 4 == 0 and W % 4 == 0
-                and tuple(unet.dec3.weight.shape) == (6, 16, 3, 3) and tuple(unet.dec2.weight.shape) == (16, 48, 3, 3)):
+        if fused:
             # dec2 + dec3 + softmax/T + blend in one persistent kernel: neither dec2's output nor refine_out is ever stored
-            dec1p, enc1p = unet.forward_until_dec1(srcs)
+            dec1p, enc1p = unet.forward_until_dec1(srcs, plan=plan)
             # u8_crop = (H, W) (DCTXVFInet.forward's emit_u8): the cropped frame rounded to 8 bits comes straight out of the kernel's fp64
             # blend instead of the fp64 frame (run_on_your_images.py:100-109 needs nothing else)
             out = fldr_hip.dec23_synth(dec1p, enc1p, unet.dec2.weight, unet.dec2.bias, unet.dec3.weight, unet.dec3.bias, cands, t4, T,
-                                       u8_crop=u8_crop, u16_crop=u16_crop)
+                                       u8_crop=u8_crop, u16_crop=u16_crop, rows=plan.dec23 if plan else None)
         elif tuple(unet.dec3.weight.shape) == (6, 16, 3, 3) and H % 2 == 0 and W % 2 == 0:
             # dec3 + softmax/T + blend in one kernel; refine_out (6 full-resolution planes) is never stored
             out = fldr_hip.dec3_synth(unet.forward_until_dec2(srcs, packed_out=fldr_hip.DEC3_MFMA and fldr_hip.use_spk()),
@@ -410,12 +425,17 @@ class PCARefineUNet(nn.Module):
             self._enc3_split = hit = (key, parts)
         return hit[1]
 
-    def forward_until_dec1(self, concat):
-        """Everything up to and including dec1 + ReLU (fLDRnet.py:621-636) on split-packed activations -> (dec1 packed [B,32,H/4,W/4],
-        enc1 packed [B,16,H/2,W/2]): the two inputs of dec2."""
-        return self.forward_until_dec2(concat, packed_out=True, stop_before_dec2=True)
+    def row_limits_ok(self):
+        """Do the encoders run as the kernels that take row limits (enc1 -> packed enc2 -> enc3 as two packed halves)?"""
+        return bool(fldr_hip.use_spk() and fldr_hip.ENC3_SPLIT and fldr_hip.s2_spk_ok(self.enc2.weight) and self._enc3_halves() is not None)
 
-    def forward_until_dec2(self, concat, packed_out=False, stop_before_dec2=False):
+    def forward_until_dec1(self, concat, plan=None):
+        """Everything up to and including dec1 + ReLU (fLDRnet.py:621-636) on split-packed activations -> (dec1 packed [B,32,H/4,W/4],
+        enc1 packed [B,16,H/2,W/2]): the two inputs of dec2.  plan (fldr_hip.SynthRows; needs row_limits_ok()): every layer produces the
+        rows the plan names and, for the encoders, reads none its producer did not write."""
+        return self.forward_until_dec2(concat, packed_out=True, stop_before_dec2=True, plan=plan)
+
+    def forward_until_dec2(self, concat, packed_out=False, stop_before_dec2=False, plan=None):
         """Everything up to and including dec2 + ReLU (fLDRnet.py:621-640), at half resolution."""
         srcs = list(concat) if isinstance(concat, (list, tuple)) else [concat]
         cv = fldr_hip.conv2d
@@ -424,11 +444,16 @@ class PCARefineUNet(nn.Module):
             # activations only exist split-packed
             cs = fldr_hip.conv2d_spk
             halves = self._enc3_halves() if fldr_hip.ENC3_SPLIT else None
+            assert plan is None or (stop_before_dec2 and self.row_limits_ok())
+            # row limits of the three encoders: the rows to produce, and the rows their producer wrote (nothing below those is read)
+            k1 = {"rows": plan.enc1, "src_rows": min(plan.prep2, plan.splat)} if plan is not None else {}
+            k2 = {"rows": plan.enc2, "src_rows": plan.enc1} if plan is not None else {}
+            k3 = {"rows": plan.enc3, "src_rows": plan.enc2} if plan is not None else {}
             if fldr_hip.s2_spk_ok(self.enc2.weight):
                 # enc2 reads enc1's PACKED output: enc1 writes no fp32 copy of its 16 half-resolution planes (141 MB at 4K)
-                enc1p = cv(srcs, self.enc1.weight, self.enc1.bias, stride=2, relu=True, want_f32=False, want_spk=True)
+                enc1p = cv(srcs, self.enc1.weight, self.enc1.bias, stride=2, relu=True, want_f32=False, want_spk=True, **k1)
                 if halves is not None:
-                    enc2, enc2p = None, fldr_hip.conv2d_s2_spk(enc1p, self.enc2.weight, self.enc2.bias, relu=True, want_f32=False, want_spk=True)
+                    enc2, enc2p = None, fldr_hip.conv2d_s2_spk(enc1p, self.enc2.weight, self.enc2.bias, relu=True, want_f32=False, want_spk=True, **k2)
                 else:
                     enc2, enc2p = fldr_hip.conv2d_s2_spk(enc1p, self.enc2.weight, self.enc2.bias, relu=True, want_f32=True, want_spk=True)
             else:
@@ -440,13 +465,14 @@ class PCARefineUNet(nn.Module):
                 # LDS; the whole layer's 128 KB only fit the per-tile kernel, which exposes a load round trip per 4-channel chunk):
                 # enc2 writes no fp32 copy either; dec0 reads the two halves as two sources
                 if fldr_hip.ENC3_PAIR:                       # ... both halves in ONE launch (round 4)
-                    out = fldr_hip.conv2d_s2_spk_pair(enc2p, halves, relu=True)
+                    out = fldr_hip.conv2d_s2_spk_pair(enc2p, halves, relu=True, **k3)
                 else:
-                    out = [fldr_hip.conv2d_s2_spk(enc2p, w, b, relu=True, want_f32=False, want_spk=True) for (w, b) in halves]
+                    out = [fldr_hip.conv2d_s2_spk(enc2p, w, b, relu=True, want_f32=False, want_spk=True, **k3) for (w, b) in halves]
             else:
                 out = [cv([enc2], self.enc3.weight, self.enc3.bias, stride=2, relu=True, want_f32=False, want_spk=True)]
-            out = cs(out, self.dec0.weight, self.dec0.bias, relu=True, want_f32=False, want_spk=True)
-            out = cs([out, enc2p], self.dec1.weight, self.dec1.bias, relu=True, up2=[True, False], want_f32=False, want_spk=True)
+            out = cs(out, self.dec0.weight, self.dec0.bias, relu=True, want_f32=False, want_spk=True, rows=plan.dec0 if plan is not None else None)
+            out = cs([out, enc2p], self.dec1.weight, self.dec1.bias, relu=True, up2=[True, False], want_f32=False, want_spk=True,
+                     rows=plan.dec1 if plan is not None else None)
             if stop_before_dec2:
                 return out, enc1p
             # dec2's output stays split-packed when the fused dec3 + blend kernel consumes it (matrix-core phase convolutions)

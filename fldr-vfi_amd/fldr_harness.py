@@ -122,7 +122,8 @@ def interpolate(model, args, frames, t_value, pyramid=None):
         if pyramid is None:
             pyramid = build_pyramid(pad_frames(frames, args), args)
         dummy = [None] * (args.S_tst + 1)          # the reference passes zero tensors that are overwritten (fLDRnet.py:134)
-        pred, _ = model(dummy, t_value, normInput=pyramid, is_training=False, validation=False)
+        # (the crop below is all the caller sees: the model's own forward need not produce the padded rows under it)
+        pred, _ = model(dummy, t_value, normInput=pyramid, is_training=False, validation=False, **({"crop": (OH, OW)} if getattr(model, "accepts_crop", False) else {}))
     return pred[:, :, :OH, :OW]
 
 

@@ -74,6 +74,11 @@ class SplatAccDesc(ctypes.Structure):
                 ("mode", ctypes.c_int32), ("flags", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class SynthRows(ctypes.Structure):
+    """fldr_synth_rows: per stage of the fused synthesis path, the output rows it has to produce (fldr_synth_row_plan)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("prep2", "splat", "enc1", "enc2", "enc3", "dec0", "dec1", "dec23")]
+
+
 class SpkConvDesc(ctypes.Structure):
     _fields_ = [
         ("src", ctypes.c_void_p * MAX_SRC),
@@ -147,6 +152,9 @@ _SIGNATURES = {
     "fldr_conv2d_s2_split": (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.c_void_p]),
     "fldr_conv2d_s2_spk": (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.c_void_p]),
     "fldr_conv2d_s2_spk_pair": (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.c_void_p]),
+    "fldr_conv2d_s2_split_rows": (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "fldr_conv2d_s2_spk_rows": (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
+    "fldr_conv2d_s2_spk_pair_rows": (ctypes.c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
     "fldr_debug_s2_persistent": (ctypes.c_int, [ctypes.c_int]),
     "fldr_debug_s2_dma": (ctypes.c_int, [ctypes.c_int]),
     "fldr_debug_s2_wgs_per_xcd": (ctypes.c_int, [ctypes.c_int]),
@@ -161,6 +169,7 @@ _SIGNATURES = {
     "fldr_conv_spk_prepack_size": (ctypes.c_int64, [ctypes.c_int] * 2),
     "fldr_conv_spk_prepack": (ctypes.c_int, [_c_float_p] * 2 + [ctypes.c_int] * 2 + [ctypes.c_void_p]),
     "fldr_conv2d_spk": (ctypes.c_int, [ctypes.POINTER(SpkConvDesc), ctypes.c_void_p]),
+    "fldr_conv2d_spk_rows": (ctypes.c_int, [ctypes.POINTER(SpkConvDesc), ctypes.c_int, ctypes.c_void_p]),
     "fldr_conv2d_spk_levels": (ctypes.c_int, [ctypes.POINTER(SpkConvDesc), ctypes.c_int, ctypes.c_void_p]),
     "fldr_debug_spk_wgs_per_xcd": (ctypes.c_int, [ctypes.c_int]),
     "fldr_range_status": (ctypes.c_int, [ctypes.c_int]),
@@ -194,6 +203,13 @@ _SIGNATURES = {
     "fldr_dec23_synth_u16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.POINTER(ctypes.c_void_p),
                                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _c_float_p, ctypes.c_double, ctypes.c_void_p]
                              + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
+    "fldr_dec23_synth_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.POINTER(ctypes.c_void_p),
+                                             ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _c_float_p, ctypes.c_double, _c_float_p, _c_float_p,
+                                             ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
+    "fldr_dec23_synth_u16_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, _c_float_p, _c_float_p, _c_float_p, _c_float_p, ctypes.POINTER(ctypes.c_void_p),
+                                                 ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), _c_float_p, ctypes.c_double, ctypes.c_void_p]
+                                  + [ctypes.c_int] * 7 + [ctypes.c_void_p]),
+    "fldr_synth_row_plan": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.POINTER(SynthRows)]),
     "fldr_ingest_u16": (ctypes.c_int, [ctypes.c_void_p, _c_float_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
     "fldr_ingest_pyramid_u16": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)] + [ctypes.c_int] * 7 + [ctypes.c_void_p]),
     "fldr_quantize_u16": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 6 + [ctypes.c_void_p]),
@@ -218,7 +234,9 @@ _DEFAULT_PATH = ("fldr_version", "fldr_error_string", "fldr_sizeof_desc", "fldr_
                  "fldr_pca_project_pyramid", "fldr_conv2d_spk", "fldr_conv2d_spk_levels", "fldr_conv_spk_prepack", "fldr_conv2d_s2_split",
                  "fldr_conv2d_s2_spk", "fldr_conv2d_s2_spk_pair", "fldr_conv_s2_prepack", "fldr_softsplat_acc64", "fldr_level0_prep",
                  "fldr_splat_bounds_upsampled_pair", "fldr_resize_bilinear_spk", "fldr_resize_bilinear_spk_bounds", "fldr_dec3_prepack_spk",
-                 "fldr_dec3_synth_spk", "fldr_spk_pack", "fldr_dec23_prepack_size", "fldr_dec23_prepack", "fldr_dec23_synth")
+                 "fldr_dec3_synth_spk", "fldr_spk_pack", "fldr_dec23_prepack_size", "fldr_dec23_prepack", "fldr_dec23_synth",
+                 "fldr_synth_row_plan", "fldr_conv2d_s2_split_rows", "fldr_conv2d_s2_spk_rows", "fldr_conv2d_s2_spk_pair_rows", "fldr_conv2d_spk_rows",
+                 "fldr_dec23_synth_rows")
 _lib = None
 _hooks_lib = None
 
@@ -542,12 +560,13 @@ def softsplat_fused(img, flow, metric, mode, out=None, scratch=None, kernel=None
     return out
 
 
-def softsplat_acc64(imgs, flows, metrics=None, mode="softmax", want_f32=True, want_spk=False, bounds_ws=None, spk_batch=False):
+def softsplat_acc64(imgs, flows, metrics=None, mode="softmax", want_f32=True, want_spk=False, bounds_ws=None, spk_batch=False, rows=None):
     """FunctionSoftsplat (softSplat.py:320-352) of one or two (img [N,C,H,W], flow [N,2,H,W]) problems of the same shape with
     destination-owned tiles and fp64 LDS atomics (fldr_softsplat_acc64): no global atomics, accumulator, memset or
     normalisation pass.  img may be a view with contiguous [H,W] planes (x_l[0][:, :, 0]); flow a batch-strided channel slice
     (up[:, :2]) whose [2,H,W] block is contiguous.  bounds_ws: per-problem bounds tables from splat_bounds_upsampled.
     spk_batch (N == 1, two problems): the packed results form ONE batch of two (sample k = problem k).
+    rows: row limit — output rows at or beyond the limit, rounded up to whole tiles (24 rows for images), are left untouched.
     -> list of fp32 tensors, of Spk tensors, or of (fp32, Spk); with spk_batch the two-sample Spk."""
     nd = len(imgs)
     assert 1 <= nd <= 2 and len(flows) == nd
@@ -597,6 +616,7 @@ def softsplat_acc64(imgs, flows, metrics=None, mode="softmax", want_f32=True, wa
         outs.append((o32, osp) if (want_f32 and want_spk) else (osp if want_spk else o32))
     d.nprob, d.N, d.C, d.H, d.W, d.mode = nd, N, C, H, W, _MODES[mode]
     d.flags = 0 if bounds_ws is None else (2 if torch.is_tensor(bounds_ws) else 1)
+    d.reserved = int(rows or 0)
     assert not torch.is_tensor(bounds_ws) or nd == 2
     _check(lib().fldr_softsplat_acc64(ctypes.byref(d), _stream()), "fldr_softsplat_acc64")
     return batch if batch is not None else outs
@@ -839,13 +859,14 @@ def resize_bilinear_spk_bounds(x, H, W, mul=1.0):
     return out, sp, ws
 
 
-def level0_prep(flow_lo, I0, I1, t, H, W, za0, za1, withmask=True, want_z=True, phase=3, state=None):
+def level0_prep(flow_lo, I0, I1, t, H, W, za0, za1, withmask=True, want_z=True, phase=3, state=None, rows2=None):
     """fLDRnet.py:400-479 minus the splats in one kernel.  flow_lo [N,4,h,w]; I0 / I1 [N,3,H,W] (batch-strided views of
     the [N,3,2,H,W] level-0 tensor, e.g. x[:, :, 0], are read in place: batch and channel strides are passed down).
     -> dict(z0, z1 (None unless want_z), flow_t0, flow_t1, flowback_0, flowback_1, im0_tot, im1_tot).
     phase=1 only fills z0 / z1 / flow_t0 / flow_t1 (what the splats need); a second call with phase=2 and state=<the dict
     returned by the first> fills flowback_* / im*_tot: the model runs the splats in between, so that enc1 reads those planes
-    right behind their producer (Infinity-Cache resident) instead of after 1.3 GB of splat traffic."""
+    right behind their producer (Infinity-Cache resident) instead of after 1.3 GB of splat traffic.
+    rows2: row limit of flowback_* / im*_tot — their rows at or beyond the limit are left untouched."""
     if state is not None:
         d, out = state["_desc"], state
         d.phase = 2 | 4
@@ -873,6 +894,7 @@ def level0_prep(flow_lo, I0, I1, t, H, W, za0, za1, withmask=True, want_z=True, 
     ws = torch.empty(N * h * w * 4, device=dev, dtype=torch.float32)
     d.ws = ws.data_ptr()
     d.phase = phase
+    d.reserved = int(rows2 or 0)
     _check(lib().fldr_level0_prep(ctypes.byref(d), _stream()), "fldr_level0_prep")
     out["_keep"] = (I0, I1, t, ws, flow_lo)
     out["_desc"] = d
@@ -1017,10 +1039,12 @@ def conv_s2_prepack(weight):
 
 
 def conv2d(srcs, weight, bias, stride=1, relu=False, residual=None, cout_store=None, up2=None, out=None, precision=None,
-           want_f32=True, want_spk=False):
+           want_f32=True, want_spk=False, rows=None, src_rows=None):
     """conv(cat(srcs, 1)) with optional fused nearest-x2 read per source, ReLU and post-activation residual.
     want_spk (exact fp32-MFMA kernels only, i.e. the stride-2 encoders): also / only emit the split-packed twin of the
     output for a following conv2d_spk; returns fp32, Spk or (fp32, Spk) like conv2d_spk.
+    rows / src_rows (the split-precision stride-2 encoders only, fldr_conv2d_s2_split_rows): output rows at or beyond `rows`, rounded up to
+    whole tile rows of 8, are left untouched; source rows at or beyond `src_rows` are zero padding and never read.
 
     srcs: list of [N,c_s,H_s,W_s] fp32 tensors whose (N, c, h, w) block may be a batch-strided view
     (e.g. feat[:, :48]) as long as each sample's [c,h,w] block is contiguous."""
@@ -1083,8 +1107,12 @@ def conv2d(srcs, weight, bias, stride=1, relu=False, residual=None, cout_store=N
     d.ksize, d.stride, d.relu, d.precision = k, stride, int(bool(relu)), (1 if (split and prec == "fp16") else 0)
     if split:
         _check(lib().fldr_conv2d_split(ctypes.byref(d), _stream()), "fldr_conv2d_split")
+    elif s2 and (rows or src_rows):
+        _check(lib().fldr_conv2d_s2_split_rows(ctypes.byref(d), int(rows or 0), int(src_rows or 0), _stream()), "fldr_conv2d_s2_split_rows")
     elif s2:
         _check(lib().fldr_conv2d_s2_split(ctypes.byref(d), _stream()), "fldr_conv2d_s2_split")
+    elif rows or src_rows:
+        raise FldrError("row limits exist for the split-precision stride-2 convolutions only")
     else:
         _check(lib().fldr_conv2d(ctypes.byref(d), _stream()), "fldr_conv2d")
     if want_spk:
@@ -1181,9 +1209,10 @@ def conv_spk_prepack(weight):
 
 
 def conv2d_spk(srcs, weight, bias, relu=False, residual=None, cout_store=None, up2=None, want_f32=True, want_spk=False,
-               precision=None):
+               precision=None, rows=None):
     """3x3 / stride-1 conv(cat(srcs, 1)) on split-packed sources (fp32 tensors are packed on the fly).  Returns the fp32
-    NCHW tensor, the Spk tensor, or (fp32, Spk) when both are asked for.  Same arithmetic as conv2d(precision='split')."""
+    NCHW tensor, the Spk tensor, or (fp32, Spk) when both are asked for.  Same arithmetic as conv2d(precision='split').
+    rows: row limit (fldr_conv2d_spk_rows) — output rows at or beyond the limit, rounded up to whole tile rows of 8, are left untouched."""
     cout, cin, k, _ = weight.shape
     assert k == 3
     up2 = up2 or [False] * len(srcs)
@@ -1225,13 +1254,16 @@ def conv2d_spk(srcs, weight, bias, relu=False, residual=None, cout_store=None, u
     prec = precision or CONV_PRECISION
     d.N, d.cin, d.cout, d.cout_store, d.H, d.W = N, cin, cout, cs, H, W
     d.relu, d.precision = int(bool(relu)), (1 if prec == "fp16" else 0) | (2 if res_packed else 0)
-    _check(lib().fldr_conv2d_spk(ctypes.byref(d), _stream()), "fldr_conv2d_spk")
+    if rows:
+        _check(lib().fldr_conv2d_spk_rows(ctypes.byref(d), int(rows), _stream()), "fldr_conv2d_spk_rows")
+    else:
+        _check(lib().fldr_conv2d_spk(ctypes.byref(d), _stream()), "fldr_conv2d_spk")
     if want_f32 and want_spk:
         return out32, outp
     return outp if want_spk else out32
 
 
-def conv2d_s2_spk(src, weight, bias, relu=False, want_f32=True, want_spk=False):
+def conv2d_s2_spk(src, weight, bias, relu=False, want_f32=True, want_spk=False, rows=None, src_rows=None):
     """The stride-2 4x4 convolution on ONE split-packed source (fldr_conv2d_s2_spk: an encoder reading the previous encoder's packed
     output, whose fp32 copy then need not exist).  -> fp32, Spk or (fp32, Spk); equal to conv2d(..., stride=2) on the unpacked
     values up to fp32 accumulation rounding.  Raises FldrError (shape) where the persistent kernel does not apply: check s2_spk_ok first."""
@@ -1252,13 +1284,16 @@ def conv2d_s2_spk(src, weight, bias, relu=False, want_f32=True, want_spk=False):
     d.N, d.cin, d.cout, d.cout_store = N, cin, cout, cout
     d.Hin, d.Win, d.Hout, d.Wout = Hin, Win, Hout, Wout
     d.ksize, d.stride, d.relu, d.precision = 4, 2, int(bool(relu)), 0
-    _check(lib().fldr_conv2d_s2_spk(ctypes.byref(d), _stream()), "fldr_conv2d_s2_spk")
+    if rows or src_rows:       # row limits as in conv2d (fldr_conv2d_s2_spk_rows)
+        _check(lib().fldr_conv2d_s2_spk_rows(ctypes.byref(d), int(rows or 0), int(src_rows or 0), _stream()), "fldr_conv2d_s2_spk_rows")
+    else:
+        _check(lib().fldr_conv2d_s2_spk(ctypes.byref(d), _stream()), "fldr_conv2d_s2_spk")
     if want_spk:
         return (out, outp) if out is not None else outp
     return out
 
 
-def conv2d_s2_spk_pair(src, halves, relu=False):
+def conv2d_s2_spk_pair(src, halves, relu=False, rows=None, src_rows=None):
     """Two stride-2 4x4 convolutions of the SAME packed source in ONE launch (fldr_conv2d_s2_spk_pair): halves = [(weight, bias), (weight,
     bias)] with equal shapes — enc3's two 32-channel halves.  -> [Spk, Spk], the bits of two conv2d_s2_spk(..., want_spk=True) calls."""
     assert isinstance(src, Spk) and len(halves) == 2
@@ -1281,7 +1316,11 @@ def conv2d_s2_spk_pair(src, halves, relu=False):
         d.ksize, d.stride, d.relu, d.precision = 4, 2, int(bool(relu)), 0
         descs.append(d)
         outs.append(outp)
-    _check(lib().fldr_conv2d_s2_spk_pair(ctypes.byref(descs[0]), ctypes.byref(descs[1]), _stream()), "fldr_conv2d_s2_spk_pair")
+    if rows or src_rows:
+        _check(lib().fldr_conv2d_s2_spk_pair_rows(ctypes.byref(descs[0]), ctypes.byref(descs[1]), int(rows or 0), int(src_rows or 0), _stream()),
+               "fldr_conv2d_s2_spk_pair_rows")
+    else:
+        _check(lib().fldr_conv2d_s2_spk_pair(ctypes.byref(descs[0]), ctypes.byref(descs[1]), _stream()), "fldr_conv2d_s2_spk_pair")
     return outs
 
 
@@ -1411,12 +1450,13 @@ def dec3_synth(d2, weight, bias, cands, t, T_param, out_dtype=torch.float64, wan
 DEC23_FUSED = os.environ.get("FLDR_DEC23", "1") != "0"
 
 
-def dec23_synth(dec1p, enc1p, w2, b2, w3, b3, cands, t, T_param, out_dtype=torch.float64, u8_crop=None, u16_crop=None, maxval=1023):
+def dec23_synth(dec1p, enc1p, w2, b2, w3, b3, cands, t, T_param, out_dtype=torch.float64, u8_crop=None, u16_crop=None, maxval=1023, rows=None):
     """PCARefineUNet.dec2 (on cat(nearest-x2(dec1), enc1), ReLU) + dec3 (on the nearest-x2 upsampled result) + softmax / T + blend
     (fLDRnet.py:638-643, 511-524) in one kernel.  dec1p: Spk [N,32,H/4,W/4]; enc1p: Spk [N,16,H/2,W/2]; w2 [16,48,3,3], w3 [6,16,3,3].
     u8_crop = (Hc, Wc) (Wc even): instead of the fp64 / fp32 frame, the frame cropped to Hc x Wc and rounded to 8 bits
     (frame_metrics' arithmetic) as a uint8 tensor [N,3,Hc,Wc].  u16_crop = (Hc, Wc) (Wc even): the same in 16-bit words with the white
-    level `maxval` (quantize_u16's arithmetic) as a uint16 tensor (fldr_dec23_synth_u16)."""
+    level `maxval` (quantize_u16's arithmetic) as a uint16 tensor (fldr_dec23_synth_u16).
+    rows: row limit — frame rows at or beyond the limit, rounded up to whole tile rows of 16, are left untouched."""
     N, c1, h4, w4 = dec1p.shape
     N2, c2, h, w = enc1p.shape
     assert isinstance(dec1p, Spk) and isinstance(enc1p, Spk) and N == N2 and c1 == 32 and c2 == 16 and h == 2 * h4 and w == 2 * w4
@@ -1454,9 +1494,12 @@ def dec23_synth(dec1p, enc1p, w2, b2, w3, b3, cands, t, T_param, out_dtype=torch
         hc, wc = int(u16_crop[0]), int(u16_crop[1])
         assert 0 < hc <= H and 0 < wc <= W and wc % 2 == 0
         out = torch.empty(N, 3, hc, wc, device=w2.device, dtype=torch.uint16)
-        _check(lib().fldr_dec23_synth_u16(ctypes.c_void_p(dec1p.ptr), ctypes.c_void_p(enc1p.ptr), _dev(w2p, "w2pack"), _dev(b2.detach(), "bias2"),
-                                          _dev(w3m, "w3m"), _dev(b3.detach(), "bias3"), ptrs, strides, cstrides, _dev(t, "t"), float(T_param),
-                                          _dev(out, "out", torch.uint16), int(maxval), hc, wc, N, H, W, _stream()), "fldr_dec23_synth_u16")
+        a16 = (ctypes.c_void_p(dec1p.ptr), ctypes.c_void_p(enc1p.ptr), _dev(w2p, "w2pack"), _dev(b2.detach(), "bias2"), _dev(w3m, "w3m"),
+               _dev(b3.detach(), "bias3"), ptrs, strides, cstrides, _dev(t, "t"), float(T_param), _dev(out, "out", torch.uint16), int(maxval), hc, wc, N, H, W)
+        if rows:
+            _check(lib().fldr_dec23_synth_u16_rows(*a16, int(rows), _stream()), "fldr_dec23_synth_u16_rows")
+        else:
+            _check(lib().fldr_dec23_synth_u16(*a16, _stream()), "fldr_dec23_synth_u16")
         return out
     if u8_crop is not None:
         hc, wc = int(u8_crop[0]), int(u8_crop[1])
@@ -1467,10 +1510,23 @@ def dec23_synth(dec1p, enc1p, w2, b2, w3, b3, cands, t, T_param, out_dtype=torch
         out = torch.empty(N, 3, H, W, device=w2.device, dtype=out_dtype)
         o64 = _dev(out, "out", torch.float64) if out_dtype == torch.float64 else None
         o32 = _dev(out, "out", torch.float32) if out_dtype == torch.float32 else None
-    _check(lib().fldr_dec23_synth(ctypes.c_void_p(dec1p.ptr), ctypes.c_void_p(enc1p.ptr), _dev(w2p, "w2pack"), _dev(b2.detach(), "bias2"), _dev(w3m, "w3m"),
-                                  _dev(b3.detach(), "bias3"), ptrs, strides, cstrides, _dev(t, "t"), float(T_param), o64, o32, o8, hc, wc, N, H, W, _stream()),
-           "fldr_dec23_synth")
+    a = (ctypes.c_void_p(dec1p.ptr), ctypes.c_void_p(enc1p.ptr), _dev(w2p, "w2pack"), _dev(b2.detach(), "bias2"), _dev(w3m, "w3m"),
+         _dev(b3.detach(), "bias3"), ptrs, strides, cstrides, _dev(t, "t"), float(T_param), o64, o32, o8, hc, wc, N, H, W)
+    if rows:
+        _check(lib().fldr_dec23_synth_rows(*a, int(rows), _stream()), "fldr_dec23_synth_rows")
+    else:
+        _check(lib().fldr_dec23_synth(*a, _stream()), "fldr_dec23_synth")
     return out
+
+
+def synth_row_plan(H, Hc):
+    """fldr_synth_row_plan: the rows every stage of the fused synthesis path has to produce for the top Hc rows of an H-row padded frame
+    -> SynthRows, or None where there is no plan (H no multiple of 8) or nothing to save (Hc >= H)."""
+    if Hc >= H or H % 8:
+        return None
+    p = SynthRows()
+    _check(lib().fldr_synth_row_plan(int(H), int(Hc), ctypes.byref(p)), "fldr_synth_row_plan")
+    return p
 
 
 INGEST_FUSED = True     # ingest + all pyramid levels in one launch (0: one launch per level)

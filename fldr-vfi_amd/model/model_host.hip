@@ -602,6 +602,15 @@ int enqueue(const fldr_model* m, const fldr_model_io* io, char* ws, const Layout
     float* w0 = (float*)(ws + L.warp0); float* w1 = (float*)(ws + L.warp1);
     float* bwimg = (float*)(ws + L.bwimg);
     const float up0 = (float)((double)Hp / L.fh[0]);
+    // The rounded output forms hold the frame's own L.H rows: every stage below produces only the rows those need (fldr_synth_row_plan) and
+    // leaves the padded rows under them untouched.  FLDR_MODEL_OUT_F64 is the whole padded frame: no limit (all zeros = all rows).
+    fldr_synth_rows rows;
+    memset(&rows, 0, sizeof(rows));
+    int src1 = 0;                                                        // rows of the frame-resolution planes enc1 may read
+    if (io->output != FLDR_MODEL_OUT_F64 && L.H < Hp) {
+        CK(fldr_synth_row_plan(Hp, L.H, &rows));
+        src1 = rows.prep2 < rows.splat ? rows.prep2 : rows.splat;
+    }
     for (int k = 0; k < io->n_t; ++k) {
         const float* t = io->t + k;
         fldr_prep_desc p;
@@ -614,6 +623,7 @@ int enqueue(const fldr_model* m, const fldr_model_io* io, char* ws, const Layout
         p.ws = (float*)(ws + L.prepws);
         p.i0_cstride = p.i1_cstride = 2 * HW;
         p.phase = 3;
+        p.reserved = rows.prep2;
         CK(fldr_level0_prep(&p, s));
         CK(fldr_splat_bounds_upsampled_pair(flow0, 0, t, 1, up0, bwimg, 1, L.fh[0], L.fw[0], Hp, Wp, s));
         fldr_splat_acc_desc a;
@@ -624,6 +634,7 @@ int enqueue(const fldr_model* m, const fldr_model_io* io, char* ws, const Layout
         a.ws[0] = a.ws[1] = bwimg;
         a.out_f32[0] = w0; a.out_f32[1] = w1;
         a.nprob = 2; a.N = 1; a.C = 3; a.H = Hp; a.W = Wp; a.mode = 3; a.flags = 2;
+        a.reserved = rows.splat;
         CK(fldr_softsplat_acc64(&a, s));
         // PCARefineUNet up to dec1 (forward_until_dec1): enc1 on the 26 planes of fLDRnet.py:480, never concatenated
         fldr_conv_desc e;
@@ -634,14 +645,14 @@ int enqueue(const fldr_model* m, const fldr_model_io* io, char* ws, const Layout
         e.n_src = 10; e.wpack = m->enc1.wpack; e.bias = m->enc1.bias; e.out_spk = ws + L.enc1p;
         e.N = 1; e.cin = 26; e.cout = 16; e.cout_store = 16; e.Hin = Hp; e.Win = Wp; e.Hout = Hp / 2; e.Wout = Wp / 2;
         e.ksize = 4; e.stride = 2; e.relu = 1; e.precision = 0;
-        CK(fldr_conv2d_s2_split(&e, s));
+        CK(fldr_conv2d_s2_split_rows(&e, rows.enc1, src1, s));
         fldr_conv_desc e2;
         memset(&e2, 0, sizeof(e2));
         e2.src[0] = (const float*)(ws + L.enc1p); e2.src_c[0] = 16; e2.n_src = 1;
         e2.wpack = m->enc2.wpack; e2.bias = m->enc2.bias; e2.out_spk = ws + L.enc2p;
         e2.N = 1; e2.cin = 16; e2.cout = 32; e2.cout_store = 32; e2.Hin = Hp / 2; e2.Win = Wp / 2; e2.Hout = Hp / 4; e2.Wout = Wp / 4;
         e2.ksize = 4; e2.stride = 2; e2.relu = 1;
-        CK(fldr_conv2d_s2_spk(&e2, s));
+        CK(fldr_conv2d_s2_spk_rows(&e2, rows.enc2, rows.enc1, s));
         fldr_conv_desc e3[2];
         for (int hf = 0; hf < 2; ++hf) {
             memset(&e3[hf], 0, sizeof(e3[hf]));
@@ -651,17 +662,17 @@ int enqueue(const fldr_model* m, const fldr_model_io* io, char* ws, const Layout
             e3[hf].Hin = Hp / 4; e3[hf].Win = Wp / 4; e3[hf].Hout = Hp / 8; e3[hf].Wout = Wp / 8;
             e3[hf].ksize = 4; e3[hf].stride = 2; e3[hf].relu = 1;
         }
-        CK(fldr_conv2d_s2_spk_pair(&e3[0], &e3[1], s));
+        CK(fldr_conv2d_s2_spk_pair_rows(&e3[0], &e3[1], rows.enc3, rows.enc2, s));
         fldr_spk_conv_desc d0 = spk_desc(m->dec0, 1, Hp / 8, Wp / 8, 1);
         add_src(d0, ws + L.enc3p[0], 0, 32, 0);
         add_src(d0, ws + L.enc3p[1], 0, 32, 0);
         d0.out_spk = ws + L.dec0p;
-        CK(fldr_conv2d_spk(&d0, s));
+        CK(fldr_conv2d_spk_rows(&d0, rows.dec0, s));
         fldr_spk_conv_desc d1 = spk_desc(m->dec1, 1, Hp / 4, Wp / 4, 1);
         add_src(d1, ws + L.dec0p, 0, 64, 1);
         add_src(d1, ws + L.enc2p, 0, 32, 0);
         d1.out_spk = ws + L.dec1p;
-        CK(fldr_conv2d_spk(&d1, s));
+        CK(fldr_conv2d_spk_rows(&d1, rows.dec1, s));
         // dec2 + dec3 + softmax / T + blend (fldr_hip.dec23_synth), in the output form asked for
         const float* cand[6] = {w0, w1, it0, it1, I0, I1};
         const int64_t cb[6] = {0, 0, 0, 0, 0, 0};
@@ -670,12 +681,12 @@ int enqueue(const fldr_model* m, const fldr_model_io* io, char* ws, const Layout
             uint16_t* o16 = (uint16_t*)io->out[k];
             if (L.W & 1) {
                 double* f64 = (double*)(ws + L.f64);
-                CK(fldr_dec23_synth(ws + L.dec1p, ws + L.enc1p, m->w2pack, m->bias2, m->w3m, m->bias3, cand, cb, cc, t, m->T, f64, nullptr, nullptr,
-                                    0, 0, 1, Hp, Wp, s));
+                CK(fldr_dec23_synth_rows(ws + L.dec1p, ws + L.enc1p, m->w2pack, m->bias2, m->w3m, m->bias3, cand, cb, cc, t, m->T, f64, nullptr, nullptr,
+                                         0, 0, 1, Hp, Wp, rows.dec23, s));
                 CK(fldr_quantize_u16(f64, 1, o16, U10_MAX, 1, L.H, L.W, Hp, Wp, s));
             } else {
-                CK(fldr_dec23_synth_u16(ws + L.dec1p, ws + L.enc1p, m->w2pack, m->bias2, m->w3m, m->bias3, cand, cb, cc, t, m->T, o16, U10_MAX,
-                                        L.H, L.W, 1, Hp, Wp, s));
+                CK(fldr_dec23_synth_u16_rows(ws + L.dec1p, ws + L.enc1p, m->w2pack, m->bias2, m->w3m, m->bias3, cand, cb, cc, t, m->T, o16, U10_MAX,
+                                             L.H, L.W, 1, Hp, Wp, rows.dec23, s));
             }
             continue;
         }
@@ -685,8 +696,8 @@ int enqueue(const fldr_model* m, const fldr_model_io* io, char* ws, const Layout
         if (io->output == FLDR_MODEL_OUT_F64) o64 = (double*)io->out[k];
         else if (L.W & 1) o64 = (double*)(ws + L.f64);                   // dec23's 8-bit form needs an even width
         else o8 = planar;
-        CK(fldr_dec23_synth(ws + L.dec1p, ws + L.enc1p, m->w2pack, m->bias2, m->w3m, m->bias3, cand, cb, cc, t, m->T, o64, nullptr, o8,
-                            o8 ? L.H : 0, o8 ? L.W : 0, 1, Hp, Wp, s));
+        CK(fldr_dec23_synth_rows(ws + L.dec1p, ws + L.enc1p, m->w2pack, m->bias2, m->w3m, m->bias3, cand, cb, cc, t, m->T, o64, nullptr, o8,
+                                 o8 ? L.H : 0, o8 ? L.W : 0, 1, Hp, Wp, rows.dec23, s));
         if (io->output != FLDR_MODEL_OUT_F64 && (L.W & 1))
             CK(fldr_frame_metrics(o64, 1, nullptr, planar, nullptr, 1, L.H, L.W, Hp, Wp, s));
         if (io->output == FLDR_MODEL_OUT_U8_INTERLEAVED)

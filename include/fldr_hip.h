@@ -26,7 +26,8 @@ extern "C" {
                                      103: fldr_range_status is 0 / 1 again, the ring status has its own entry (fldr_ring_status),
                                      fldr_enc1_fused; 104: fldr_dec23_prepack / fldr_dec23_synth (with the rounded 8-bit frame as a
                                      third output form); 105: fldr_status_word (status readable without synchronising; frames after a ring fault are NaN)
-                                     — a caller built against an older header must be rebuilt */
+                                     — a caller built against an older header must be rebuilt; still 105: fldr_synth_row_plan and the
+                                     row-limited entry points (*_rows, the `reserved` words of fldr_prep_desc / fldr_splat_acc_desc) are additions */
 
 #define FLDR_E_ARG   (-1)         /* bad argument (null pointer, non-positive size, unsupported shape) */
 #define FLDR_E_SHAPE (-2)         /* shape constraint violated (e.g. H,W not multiples of 8 for the PCA) */
@@ -113,7 +114,9 @@ typedef struct fldr_splat_acc_desc {
     float*       ws[2];
     float*       out_f32[2];
     void*        out_spk[2];
-    int32_t      nprob, N, C, H, W, mode, flags, reserved;
+    int32_t      nprob, N, C, H, W, mode, flags;
+    int32_t      reserved;      /* destination rows to produce (the tiles, 24 rows for images, that start below it), 0 = all: rows at or beyond
+                                   the rounded-up limit are left untouched (fldr_synth_row_plan.splat) */
 } fldr_splat_acc_desc;
 FLDR_API int fldr_softsplat_acc64(const fldr_splat_acc_desc* desc, fldr_stream_t stream);
 
@@ -262,7 +265,8 @@ typedef struct fldr_prep_desc {
     int32_t phase;                   /* 0 or 3: everything in one launch; 1: only z0 / z1 + flow_t0 / flow_t1 (what the splats need);
                                         2 | 4 = 6: only flowback_* + im*_tot, reusing the workspace filled by a phase-1 call — so that
                                         the consumer of those planes (enc1) can run right behind their producer */
-    int32_t reserved;
+    int32_t reserved;                /* rows of flowback_* / im*_tot to produce, 0 = all: their rows at or beyond it are left untouched
+                                        (fldr_synth_row_plan.prep2); z0 / z1 / flow_t0 / flow_t1 always have every row */
 } fldr_prep_desc;
 FLDR_API int fldr_level0_prep(const fldr_prep_desc* desc, fldr_stream_t stream);
 
@@ -330,6 +334,13 @@ FLDR_API int fldr_conv2d_s2_spk(const fldr_conv_desc* desc, fldr_stream_t stream
  * the two 32-channel halves of enc3 (fLDRnet.py:617).  The bits of two fldr_conv2d_s2_spk calls. */
 FLDR_API int fldr_conv2d_s2_spk_pair(const fldr_conv_desc* desc0, const fldr_conv_desc* desc1, fldr_stream_t stream);
 FLDR_API int fldr_conv2d_s2_split(const fldr_conv_desc* desc, fldr_stream_t stream);
+/* The three stride-2 entry points with row limits (0 = none; with 0, 0 they ARE the calls above): only the tile rows (8 output rows) that
+ * hold output rows below out_rows are computed — output rows at or beyond the rounded-up limit are left untouched —, and a source row at
+ * or beyond src_rows (<= Hin: the rows the source's producer wrote) is treated as zero padding and never read.  Output rows whose 4 x 4
+ * windows lie below src_rows are the bits of the unlimited call. */
+FLDR_API int fldr_conv2d_s2_split_rows(const fldr_conv_desc* desc, int out_rows, int src_rows, fldr_stream_t stream);
+FLDR_API int fldr_conv2d_s2_spk_rows(const fldr_conv_desc* desc, int out_rows, int src_rows, fldr_stream_t stream);
+FLDR_API int fldr_conv2d_s2_spk_pair_rows(const fldr_conv_desc* desc0, const fldr_conv_desc* desc1, int out_rows, int src_rows, fldr_stream_t stream);
 
 /* Split-packed ("SPK") activations: the layout convolution outputs take when their consumer is another convolution.
  * A logical [N,C,H,W] fp32 tensor is stored as [N][G=ceil(C/8)][hi,lo][H*W][8 x fp16] (x = hi + lo, 22 significant
@@ -362,6 +373,10 @@ FLDR_API int fldr_spk_unpack(const void* src, float* dst, int N, int C, int H, i
 FLDR_API int64_t fldr_conv_spk_prepack_size(int cout, int cin);             /* floats */
 FLDR_API int fldr_conv_spk_prepack(const float* weight, float* wpack, int cout, int cin, fldr_stream_t stream);
 FLDR_API int fldr_conv2d_spk(const fldr_spk_conv_desc* desc, fldr_stream_t stream);
+/* The same with a row limit (0 = none): only the tile rows (8 output rows) that hold output rows below `rows` are computed, from source rows
+ * <= the rounded-up limit (>> 1 for an x2 source); output rows at or beyond the rounded-up limit are left untouched, the others are the bits
+ * of fldr_conv2d_spk. */
+FLDR_API int fldr_conv2d_spk_rows(const fldr_spk_conv_desc* desc, int rows, fldr_stream_t stream);
 /* The same convolution (shared wpack / bias / relu / channel counts / precision) over n_levels (<= 8) inputs of different sizes in ONE
  * launch of the ring pipeline — rec_ctx_ds over the pyramid levels (fLDRnet.py:148-162 runs it level by level).  Every entry:
  * N = 1, one packed source; residual / out_f32 / out_spk for all entries or none.  Results are the bits of n_levels separate
@@ -443,12 +458,35 @@ FLDR_API int fldr_dec23_prepack(const float* dec2_weight, float* wpack, fldr_str
 FLDR_API int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
                      const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
                      double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, fldr_stream_t stream);
+/* fldr_dec23_synth with a row limit (0 = none): the tile walk stops at the tile row (16 frame rows) that holds frame row rows - 1; frame rows at
+ * or beyond the rounded-up limit are left untouched (rows of the 8-bit form beyond H_u8 do not exist anyway), the others are the bits of
+ * fldr_dec23_synth.  Reads enc1 rows < 8 R + 2 and dec1 rows < 4 R + 1 for R tile rows. */
+FLDR_API int fldr_dec23_synth_rows(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
+                     const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
+                     double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, int rows, fldr_stream_t stream);
 /* The same kernel with the rounded frame in 16-bit words: out_u16 [N,3,H_u16,W_u16] = rint(clamp((x + 1) / 2, 0, 1) * maxval) (half to even;
  * maxval = 1023 for 10-bit material; a NaN — a poisoned frame — gives 0), the arithmetic of fldr_quantize_u16 straight from the fp64 blend.
  * W_u16 even, out_u16 4-byte aligned (two pixels are one 32-bit store); every other argument as fldr_dec23_synth. */
 FLDR_API int fldr_dec23_synth_u16(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
                      const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
                      uint16_t* out_u16, int maxval, int H_u16, int W_u16, int N, int H, int W, fldr_stream_t stream);
+FLDR_API int fldr_dec23_synth_u16_rows(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
+                     const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
+                     uint16_t* out_u16, int maxval, int H_u16, int W_u16, int N, int H, int W, int rows, fldr_stream_t stream);
+
+/* Which rows the synthesis half (fLDRnet.py:400-535 on the fused path: fldr_level0_prep, the image splats, enc1 .. dec1, fldr_dec23_synth)
+ * has to produce when only the top Hc rows of the H-row padded frame are shown (DCTXVFInet.forward crops to 2160 rows, fLDRnet.py:222; the
+ * drivers crop to the frame): per stage, in its own output rows, the value to pass as that stage's row limit — derived backwards from the
+ * crop through the receptive fields and tile heights (csrc/row_plan.h).  enc1 takes src_rows = min(prep2, splat), enc2 src_rows = enc1,
+ * enc3 src_rows = enc2.  H a multiple of 8 (FLDR_E_SHAPE otherwise), 0 < Hc <= H; Hc == H gives every stage all its rows.  Host code only. */
+typedef struct fldr_synth_rows {
+    int32_t prep2;             /* fldr_prep_desc.reserved */
+    int32_t splat;             /* fldr_splat_acc_desc.reserved of the image splats */
+    int32_t enc1, enc2, enc3;  /* out_rows of the stride-2 convolutions */
+    int32_t dec0, dec1;        /* rows of fldr_conv2d_spk_rows */
+    int32_t dec23;             /* rows of fldr_dec23_synth_rows */
+} fldr_synth_rows;
+FLDR_API int fldr_synth_row_plan(int H, int Hc, fldr_synth_rows* plan);
 
 /* ------------------------------------------------------------------------------------------
  * Callers either side of the path, on the device (the reference does these on the CPU).
