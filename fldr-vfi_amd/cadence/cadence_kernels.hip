@@ -66,8 +66,8 @@ __global__ __launch_bounds__(RK_THREADS) void repeat_tiles_kernel(RepeatArgs a) 
             const uint8_t* p1 = a.y[1] + (int64_t)row * a.pitch[1] + off;
             if (left >= 16) {
                 uint32_t d0[4], d1[4];
-                load16<MODE, VEC>(p0, d0);
-                load16<MODE, VEC>(p1, d1);
+                load16<MODE != Y8_BYTE, VEC>(p0, d0);
+                load16<MODE != Y8_BYTE, VEC>(p1, d1);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const uint32_t u = reduce8<MODE>(d0[i]), v = reduce8<MODE>(d1[i]);
@@ -142,7 +142,7 @@ int repeat_measure(const void* y0, int64_t pitch0, const void* y1, int64_t pitch
     const uint32_t bx = min((a.tiles_x + RK_WAVES - 1) / RK_WAVES, (uint32_t)RK_MAX_BLOCKS);
     const dim3 blocks(bx, min(a.tiles_y, (uint32_t)RK_MAX_BLOCKS / bx));
     repeat_zero_kernel<<<1, RK_THREADS, 0, stream>>>(a.state);
-    LUMA8_LAUNCH(repeat_tiles_kernel, mode, vec, blocks, RK_THREADS, stream, a);
+    SAMPLE16_LAUNCH(repeat_tiles_kernel, mode, vec, blocks, RK_THREADS, stream, a);
     repeat_result_kernel<<<1, 64, 0, stream>>>(a.state);
     return (int)hipGetLastError();
 }

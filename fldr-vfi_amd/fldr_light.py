@@ -11,8 +11,9 @@ instead of on code values: every sample through a transfer curve (a table) befor
     outs = c.push((y, u, v)); ...; outs = c.flush()              # as fldr_shutter.Converter: c.last_info, c.last_scene
 
 table(transfer, depth) is the host-only fldr_light_table: the words a built-in curve holds, what the tests feed their oracle.  Windows
-and pushes are fldr_shutter's (fldr_shutter.schedule).  Every kernel call and forward enqueues on torch's current stream and returns
-without synchronising.  No fallback: a missing library raises at load.
+and pushes are fldr_shutter's (fldr_shutter.schedule), and so is the code under the three kernel calls, the forward and the converter
+(fldr_shutter._accumulate / _resolve / _mix, _NativeForward, _WindowStream): this module adds the curve and scratch.  Every kernel call and
+forward enqueues on torch's current stream and returns without synchronising.  No fallback: a missing library raises at load.
 """
 import ctypes
 import os
@@ -22,10 +23,9 @@ import torch
 
 import fldr_model
 import fldr_shutter
-import fldr_video
 from fldr_rate import SceneResult
 from fldr_shutter import Info, ShutterConfig
-from fldr_video import Format, Frame, IO, _stream_ptr, empty_frame, frame_struct
+from fldr_video import Format, Frame, IO, _stream_ptr  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfldr_light.so")
@@ -85,17 +85,14 @@ def lib():
     return _lib
 
 
-def _check(code, what):
-    if code != 0:
-        raise LightError(what, code)
+_API = fldr_shutter._Api(lib, "fldr_light", LightError)
 
 
 # ---- the curve --------------------------------------------------------------------------------------------------------------------------
 def table(transfer, depth=8):
     """fldr_light_table: the built-in table of "gamma24" / "pq" / "hlg" at depth 8 or 10 -> uint32 numpy [2^depth].  Host only."""
     lin = np.zeros(1 << (depth or 8), np.uint32)
-    _check(lib().fldr_light_table(TRANSFERS[transfer] if isinstance(transfer, str) else int(transfer), int(depth),
-                                  lin.ctypes.data_as(_U32P)), "fldr_light_table")
+    _API.call("table", TRANSFERS[transfer] if isinstance(transfer, str) else int(transfer), int(depth), lin.ctypes.data_as(_U32P))
     return lin
 
 
@@ -113,7 +110,7 @@ class Curve:
             ptr = None
         self.depth = depth or 8
         self._h = ctypes.c_void_p()
-        _check(lib().fldr_light_curve_create(TRANSFERS[transfer], int(depth), ptr, int(device), ctypes.byref(self._h)), "fldr_light_curve_create")
+        _API.call("curve_create", TRANSFERS[transfer], int(depth), ptr, int(device), ctypes.byref(self._h))
 
     def close(self):
         if self._h is not None and self._h.value:
@@ -129,142 +126,61 @@ class Curve:
 
 # ---- the integration kernels --------------------------------------------------------------------------------------------------------------
 def acc_bytes(H, W):
-    n = lib().fldr_light_acc_bytes(int(H), int(W))
-    if n < 0:
-        raise LightError("fldr_light_acc_bytes", int(n))
-    return int(n)
+    return _API.size("acc_bytes", int(H), int(W))
 
 
 def scratch_bytes(H, W, fmt):
-    n = lib().fldr_light_scratch_bytes(int(H), int(W), ctypes.byref(fmt))
-    if n < 0:
-        raise LightError("fldr_light_scratch_bytes", int(n))
-    return int(n)
+    return _API.size("scratch_bytes", int(H), int(W), ctypes.byref(fmt))
 
 
 def _scratch(scratch, H, W, fmt, device):
     return scratch if scratch is not None else torch.empty(scratch_bytes(H, W, fmt), dtype=torch.uint8, device=device)
 
 
-def _frames_weights(frames, weights):
-    arr = (Frame * len(frames))(*[frame_struct(f) for f in frames])
-    w = (ctypes.c_int32 * len(weights))(*[int(v) for v in weights])
-    return arr, w
-
-
+# The three calls are fldr_shutter's with the curve behind fmt and scratch before the stream.
 def accumulate(curve, frames, weights, fmt, acc=None, first=True, scratch=None, stream=None):
     """fldr_light_accumulate of device frames; acc: a uint8 device tensor of acc_bytes (allocated otherwise) -> acc."""
     H, W = frames[0][0].shape
-    device = frames[0][0].device
-    if acc is None:
-        acc = torch.empty(acc_bytes(H, W), dtype=torch.uint8, device=device)
-    scratch = _scratch(scratch, H, W, fmt, device)
-    arr, w = _frames_weights(frames, weights)
-    _check(lib().fldr_light_accumulate(int(H), int(W), ctypes.byref(fmt), curve._h, arr, w, len(frames), 1 if first else 0,
-                                       ctypes.c_void_p(acc.data_ptr()), ctypes.c_void_p(scratch.data_ptr()), _stream_ptr(device, stream)),
-           "fldr_light_accumulate")
-    return acc
+    scratch = _scratch(scratch, H, W, fmt, frames[0][0].device)
+    return fldr_shutter._accumulate(_API, (curve._h,), (ctypes.c_void_p(scratch.data_ptr()),), frames, weights, fmt, acc, acc_bytes, first, stream)
 
 
 def resolve(curve, acc, total, H, W, fmt, out=None, scratch=None, stream=None):
     """fldr_light_resolve -> one device frame (`out` when given; allocated packed otherwise)."""
-    if out is None:
-        out = empty_frame(fmt, H, W, acc.device)
     scratch = _scratch(scratch, H, W, fmt, acc.device)
-    fr = frame_struct(out)
-    _check(lib().fldr_light_resolve(int(H), int(W), ctypes.byref(fmt), curve._h, ctypes.c_void_p(acc.data_ptr()), int(total), ctypes.byref(fr),
-                                    ctypes.c_void_p(scratch.data_ptr()), _stream_ptr(acc.device, stream)), "fldr_light_resolve")
-    return out
+    return fldr_shutter._resolve(_API, (curve._h,), (ctypes.c_void_p(scratch.data_ptr()),), acc, total, H, W, fmt, out, stream)
 
 
 def mix(curve, frames, weights, fmt, out=None, scratch=None, stream=None):
     """fldr_light_mix of device frames -> one device frame."""
     H, W = frames[0][0].shape
-    device = frames[0][0].device
-    if out is None:
-        out = empty_frame(fmt, H, W, device)
-    scratch = _scratch(scratch, H, W, fmt, device)
-    arr, w = _frames_weights(frames, weights)
-    fr = frame_struct(out)
-    _check(lib().fldr_light_mix(int(H), int(W), ctypes.byref(fmt), curve._h, arr, w, len(frames), ctypes.byref(fr),
-                                ctypes.c_void_p(scratch.data_ptr()), _stream_ptr(device, stream)), "fldr_light_mix")
-    return out
+    scratch = _scratch(scratch, H, W, fmt, frames[0][0].device)
+    return fldr_shutter._mix(_API, (curve._h,), (ctypes.c_void_p(scratch.data_ptr()),), frames, weights, fmt, out, stream)
 
 
-class NativeLight(fldr_video.NativeVideo):
+class NativeLight(fldr_shutter._NativeForward):
     """fldr_light_forward on a fldr_model.NativeModel: NativeVideo's forward, then one linear-light mix of its planar frames."""
 
-    def __init__(self, native_model):
-        lib()
-        super().__init__(native_model)
-
-    def workspace_bytes(self, H, W, n_t=1):
-        n = lib().fldr_light_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
-        if n < 0:
-            raise LightError("fldr_light_workspace_bytes", int(n))
-        return int(n)
+    _api = _API
 
     def forward_io(self, io, curve, w0, w1, w, ws, stream=None):
         """The raw call; returns the code without raising."""
-        wa = (ctypes.c_int32 * len(w))(*[int(v) for v in w]) if w is not None else None
-        return lib().fldr_light_forward(self.model._h, ctypes.byref(io) if io is not None else None, curve._h if curve is not None else None,
-                                        int(w0), int(w1), wa, ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
-                                        ws.numel() if ws is not None else 0, _stream_ptr(self.device, stream))
+        return self._forward_io(io, (curve._h if curve is not None else None,), w0, w1, w, ws, stream)
 
     def forward(self, curve, frames, t, weights, fmt=None, out=None, ws=None, stream=None):
         """frames: (I0, I1) in fmt; t: the n_t sub-frame times; weights: (w0, w1, [w of each sub-frame]).  -> the one output frame."""
-        fmt = fmt or Format()
-        H, W = frames[0][0].shape
-        tt = self._t(t)
-        n_t = tt.numel()
-        if out is None:
-            out = empty_frame(fmt, H, W, self.device)
-        if ws is None:
-            ws = self.workspace(H, W, n_t)
-        io = self.make_io(frames, tt, fmt, fmt, [out], H, W)
-        io.n_t = n_t
-        w0, w1, w = weights
-        _check(self.forward_io(io, curve, w0, w1, w, ws, stream), "fldr_light_forward")
-        return out
+        return self._forward((curve._h if curve is not None else None,), frames, t, weights, fmt, out, ws, stream)
 
 
-class Converter(fldr_video.HostStream):
+class Converter(fldr_shutter._WindowStream):
     """fldr_light: fldr_shutter.Converter with every output the linear-light mean of its points."""
 
-    _destroy = staticmethod(lambda h: lib().fldr_light_destroy(h))
+    _api = _API
 
     def __init__(self, native_model, curve, H, W, fmt=None, in_rate=120, out_rate=24, shutter=(1, 2), sub=1, scene=True, params=None):
         fmt = fmt or Format()
         cfg = LightConfig()
         cfg.shutter = fldr_shutter.config(in_rate, out_rate, shutter, sub, H, W, fmt, native_model.device.index or 0, scene, params)
         cfg.curve = curve._h
-        self._h = ctypes.c_void_p()
-        self.model, self.curve = native_model, curve                 # the converter uses both: keep them alive
-        _check(lib().fldr_light_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_light_create")
-        self.H, self.W, self.format = int(H), int(W), fmt
-        self.max_out = lib().fldr_light_max_out(self._h)
-        self._stage(fmt, H, W, self.max_out)
-        self._info = (Info * self.max_out)()
-        self.last_scene, self.last_info = None, []
-
-    def _done(self, n):
-        self.last_info = [self._info[k].as_dict() for k in range(n)]
-        return self._taken(n)
-
-    def push(self, frame):
-        """-> the list of output frames due (tuples of numpy planes, fresh copies); self.last_info, self.last_scene."""
-        fr = frame_struct(frame)
-        n = ctypes.c_int(-1)
-        res = SceneResult()
-        _check(lib().fldr_light_push(self._h, ctypes.byref(fr), self._out_structs(), self._info, ctypes.byref(n), ctypes.byref(res)),
-               "fldr_light_push")
-        self.last_scene = res.as_dict()
-        return self._done(n.value)
-
-    def flush(self):
-        n = ctypes.c_int(-1)
-        _check(lib().fldr_light_flush(self._h, self._out_structs(), self._info, ctypes.byref(n)), "fldr_light_flush")
-        return self._done(n.value)
-
-    def reset(self):
-        _check(lib().fldr_light_reset(self._h), "fldr_light_reset")
+        self.curve = curve                                           # the converter uses the curve as well as the model: keep it alive
+        self._open(native_model, cfg, H, W, fmt)

@@ -90,9 +90,34 @@ def lib():
     return _lib
 
 
-def _check(code, what):
-    if code != 0:
-        raise ShutterError(what, code)
+class _Api:
+    """A library as the code this module shares with fldr_light calls it: fldr_<prefix>_<name>(*args) of lib(), a refusal raised as the
+    library's own error class."""
+
+    def __init__(self, lib, prefix, error):
+        self.lib, self.prefix, self.error, self._fns = lib, prefix, error, {}
+
+    def fn(self, name):
+        f = self._fns.get(name)
+        if f is None:
+            f = self._fns[name] = getattr(self.lib(), "%s_%s" % (self.prefix, name))
+        return f
+
+    def call(self, name, *args):
+        """A function that returns a code."""
+        code = (self._fns.get(name) or self.fn(name))(*args)
+        if code != 0:
+            raise self.error("%s_%s" % (self.prefix, name), code)
+
+    def size(self, name, *args):
+        """A function that returns a number of bytes, or a negative code."""
+        n = self.fn(name)(*args)
+        if n < 0:
+            raise self.error("%s_%s" % (self.prefix, name), int(n))
+        return int(n)
+
+
+_API = _Api(lib, "fldr_shutter", ShutterError)
 
 
 # ---- the window rule and the schedule -----------------------------------------------------------------------------------------------------
@@ -112,7 +137,7 @@ def config(in_rate, out_rate, shutter=(1, 2), sub=1, H=0, W=0, fmt=None, device=
 def plan(cfg, j):
     """fldr_shutter_plan: (first, last) grid point of output j's window.  Host only."""
     f, l = ctypes.c_int64(), ctypes.c_int64()
-    _check(lib().fldr_shutter_plan(ctypes.byref(cfg), int(j), ctypes.byref(f), ctypes.byref(l)), "fldr_shutter_plan")
+    _API.call("plan", ctypes.byref(cfg), int(j), ctypes.byref(f), ctypes.byref(l))
     return f.value, l.value
 
 
@@ -166,83 +191,90 @@ def schedule(n_frames, in_rate, out_rate, shutter=(1, 2), sub=1, cuts=()):
 
 # ---- the integration kernels --------------------------------------------------------------------------------------------------------------
 def acc_bytes(H, W, fmt):
-    n = lib().fldr_shutter_acc_bytes(int(H), int(W), ctypes.byref(fmt))
-    if n < 0:
-        raise ShutterError("fldr_shutter_acc_bytes", int(n))
-    return int(n)
+    return _API.size("acc_bytes", int(H), int(W), ctypes.byref(fmt))
 
 
 def reciprocal(total):
     """(mul, shift) resolve divides by 2 total with."""
     m, s = ctypes.c_uint32(), ctypes.c_uint32()
-    _check(lib().fldr_shutter_reciprocal(int(total), ctypes.byref(m), ctypes.byref(s)), "fldr_shutter_reciprocal")
+    _API.call("reciprocal", int(total), ctypes.byref(m), ctypes.byref(s))
     return m.value, s.value
 
 
+def _i32(values):
+    return (ctypes.c_int32 * len(values))(*[int(v) for v in values])
+
+
 def _frames_weights(frames, weights):
-    arr = (Frame * len(frames))(*[frame_struct(f) for f in frames])
-    w = (ctypes.c_int32 * len(weights))(*[int(v) for v in weights])
-    return arr, w
+    return (Frame * len(frames))(*[frame_struct(f) for f in frames]), (ctypes.c_int32 * len(weights))(*[int(v) for v in weights])
 
 
-def accumulate(frames, weights, fmt, acc=None, first=True, stream=None):
-    """fldr_shutter_accumulate of device frames; acc: a uint8 device tensor of acc_bytes (allocated otherwise) -> acc."""
+# accumulate / resolve / mix of this library and of fldr_light: `lead` is what the library's function takes behind fmt (light: the curve),
+# `trail` what it takes before the stream (light: the pointer to scratch).  acc: a uint8 device tensor of the library's acc_bytes, or None.
+def _accumulate(api, lead, trail, frames, weights, fmt, acc, acc_size, first, stream):
     H, W = frames[0][0].shape
     device = frames[0][0].device
     if acc is None:
-        acc = torch.empty(acc_bytes(H, W, fmt), dtype=torch.uint8, device=device)
+        acc = torch.empty(acc_size(H, W), dtype=torch.uint8, device=device)
     arr, w = _frames_weights(frames, weights)
-    _check(lib().fldr_shutter_accumulate(int(H), int(W), ctypes.byref(fmt), arr, w, len(frames), 1 if first else 0, ctypes.c_void_p(acc.data_ptr()),
-                                         _stream_ptr(device, stream)), "fldr_shutter_accumulate")
+    api.call("accumulate", int(H), int(W), ctypes.byref(fmt), *lead, arr, w, len(frames), 1 if first else 0, ctypes.c_void_p(acc.data_ptr()), *trail,
+             _stream_ptr(device, stream))
     return acc
 
 
-def resolve(acc, total, H, W, fmt, out=None, stream=None):
-    """fldr_shutter_resolve -> one device frame (`out` when given; allocated packed otherwise)."""
+def _resolve(api, lead, trail, acc, total, H, W, fmt, out, stream):
     if out is None:
         out = empty_frame(fmt, H, W, acc.device)
     fr = frame_struct(out)
-    _check(lib().fldr_shutter_resolve(int(H), int(W), ctypes.byref(fmt), ctypes.c_void_p(acc.data_ptr()), int(total), ctypes.byref(fr),
-                                      _stream_ptr(acc.device, stream)), "fldr_shutter_resolve")
+    api.call("resolve", int(H), int(W), ctypes.byref(fmt), *lead, ctypes.c_void_p(acc.data_ptr()), int(total), ctypes.byref(fr), *trail,
+             _stream_ptr(acc.device, stream))
     return out
 
 
-def mix(frames, weights, fmt, out=None, stream=None):
-    """fldr_shutter_mix of device frames -> one device frame."""
+def _mix(api, lead, trail, frames, weights, fmt, out, stream):
     H, W = frames[0][0].shape
     device = frames[0][0].device
     if out is None:
         out = empty_frame(fmt, H, W, device)
     arr, w = _frames_weights(frames, weights)
     fr = frame_struct(out)
-    _check(lib().fldr_shutter_mix(int(H), int(W), ctypes.byref(fmt), arr, w, len(frames), ctypes.byref(fr), _stream_ptr(device, stream)),
-           "fldr_shutter_mix")
+    api.call("mix", int(H), int(W), ctypes.byref(fmt), *lead, arr, w, len(frames), ctypes.byref(fr), *trail,
+             _stream_ptr(device, stream))
     return out
 
 
-class NativeShutter(fldr_video.NativeVideo):
-    """fldr_shutter_forward on a fldr_model.NativeModel: NativeVideo's forward into scratch frames, then one mix."""
+def accumulate(frames, weights, fmt, acc=None, first=True, stream=None):
+    """fldr_shutter_accumulate of device frames; acc: a uint8 device tensor of acc_bytes (allocated otherwise) -> acc."""
+    return _accumulate(_API, (), (), frames, weights, fmt, acc, lambda H, W: acc_bytes(H, W, fmt), first, stream)
+
+
+def resolve(acc, total, H, W, fmt, out=None, stream=None):
+    """fldr_shutter_resolve -> one device frame (`out` when given; allocated packed otherwise)."""
+    return _resolve(_API, (), (), acc, total, H, W, fmt, out, stream)
+
+
+def mix(frames, weights, fmt, out=None, stream=None):
+    """fldr_shutter_mix of device frames -> one device frame."""
+    return _mix(_API, (), (), frames, weights, fmt, out, stream)
+
+
+class _NativeForward(fldr_video.NativeVideo):
+    """What NativeShutter and fldr_light.NativeLight share: the library's forward on a fldr_model.NativeModel.  A subclass names its
+    library (`_api`) and gives forward_io / forward its own signature: `lead` is what its forward takes behind io (light: the curve)."""
 
     def __init__(self, native_model):
-        lib()
+        self._api.lib()
         super().__init__(native_model)
 
     def workspace_bytes(self, H, W, n_t=1):
-        n = lib().fldr_shutter_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
-        if n < 0:
-            raise ShutterError("fldr_shutter_workspace_bytes", int(n))
-        return int(n)
+        return self._api.size("workspace_bytes", self.model._h, int(H), int(W), int(n_t))
 
-    def forward_io(self, io, w0, w1, w, ws, stream=None):
-        """The raw call; returns the code without raising."""
-        wa = (ctypes.c_int32 * len(w))(*[int(v) for v in w]) if w is not None else None
-        return lib().fldr_shutter_forward(self.model._h, ctypes.byref(io) if io is not None else None, int(w0), int(w1), wa,
-                                          ctypes.c_void_p(ws.data_ptr()) if ws is not None else None, ws.numel() if ws is not None else 0,
-                                          _stream_ptr(self.device, stream))
+    def _forward_io(self, io, lead, w0, w1, w, ws, stream):
+        return self._api.fn("forward")(self.model._h, ctypes.byref(io) if io is not None else None, *lead, int(w0), int(w1),
+                                       _i32(w) if w is not None else None, ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                       ws.numel() if ws is not None else 0, _stream_ptr(self.device, stream))
 
-    def forward(self, frames, t, weights, fmt=None, out=None, ws=None, stream=None):
-        """frames: (I0, I1) in fmt; t: the n_t sub-frame times as NativeVideo.forward takes them; weights: (w0, w1, [w of each
-        sub-frame]).  -> the one output frame."""
+    def _forward(self, lead, frames, t, weights, fmt, out, ws, stream):
         fmt = fmt or Format()
         H, W = frames[0][0].shape
         tt = self._t(t)
@@ -254,24 +286,42 @@ class NativeShutter(fldr_video.NativeVideo):
         io = self.make_io(frames, tt, fmt, fmt, [out], H, W)
         io.n_t = n_t
         w0, w1, w = weights
-        _check(self.forward_io(io, w0, w1, w, ws, stream), "fldr_shutter_forward")
+        code = self._forward_io(io, lead, w0, w1, w, ws, stream)
+        if code != 0:
+            raise self._api.error(self._api.prefix + "_forward", code)
         return out
 
 
-class Converter(fldr_video.HostStream):
-    """fldr_shutter: host frames (tuples of numpy planes) pushed one by one at in_rate; each push returns the output frames at out_rate
-    whose exposure window it completes (schedule()), flush() the one still open."""
+class NativeShutter(_NativeForward):
+    """fldr_shutter_forward on a fldr_model.NativeModel: NativeVideo's forward into scratch frames, then one mix."""
 
-    _destroy = staticmethod(lambda h: lib().fldr_shutter_destroy(h))
+    _api = _API
 
-    def __init__(self, native_model, H, W, fmt=None, in_rate=120, out_rate=24, shutter=(1, 2), sub=1, scene=True, params=None):
-        fmt = fmt or Format()
-        cfg = config(in_rate, out_rate, shutter, sub, H, W, fmt, native_model.device.index or 0, scene, params)
+    def forward_io(self, io, w0, w1, w, ws, stream=None):
+        """The raw call; returns the code without raising."""
+        return self._forward_io(io, (), w0, w1, w, ws, stream)
+
+    def forward(self, frames, t, weights, fmt=None, out=None, ws=None, stream=None):
+        """frames: (I0, I1) in fmt; t: the n_t sub-frame times as NativeVideo.forward takes them; weights: (w0, w1, [w of each
+        sub-frame]).  -> the one output frame."""
+        return self._forward((), frames, t, weights, fmt, out, ws, stream)
+
+
+class _WindowStream(fldr_video.HostStream):
+    """What Converter and fldr_light.Converter share: the handle of a converter of the library `_api` over the window rule, the staged
+    outputs and their Info, push / flush / reset.  A subclass builds its config and hands it to _open."""
+
+    _api = _API
+
+    def _destroy(self, h):
+        self._api.fn("destroy")(h)
+
+    def _open(self, native_model, cfg, H, W, fmt):
         self._h = ctypes.c_void_p()
         self.model = native_model                                    # the converter uses the model: keep it alive
-        _check(lib().fldr_shutter_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_shutter_create")
+        self._api.call("create", native_model._h, ctypes.byref(cfg), ctypes.byref(self._h))
         self.H, self.W, self.format = int(H), int(W), fmt
-        self.max_out = lib().fldr_shutter_max_out(self._h)
+        self.max_out = self._api.fn("max_out")(self._h)
         self._stage(fmt, H, W, self.max_out)
         self._info = (Info * self.max_out)()
         self.last_scene, self.last_info = None, []
@@ -285,15 +335,23 @@ class Converter(fldr_video.HostStream):
         fr = frame_struct(frame)
         n = ctypes.c_int(-1)
         res = SceneResult()
-        _check(lib().fldr_shutter_push(self._h, ctypes.byref(fr), self._out_structs(), self._info, ctypes.byref(n), ctypes.byref(res)),
-               "fldr_shutter_push")
+        self._api.call("push", self._h, ctypes.byref(fr), self._out_structs(), self._info, ctypes.byref(n), ctypes.byref(res))
         self.last_scene = res.as_dict()
         return self._done(n.value)
 
     def flush(self):
         n = ctypes.c_int(-1)
-        _check(lib().fldr_shutter_flush(self._h, self._out_structs(), self._info, ctypes.byref(n)), "fldr_shutter_flush")
+        self._api.call("flush", self._h, self._out_structs(), self._info, ctypes.byref(n))
         return self._done(n.value)
 
     def reset(self):
-        _check(lib().fldr_shutter_reset(self._h), "fldr_shutter_reset")
+        self._api.call("reset", self._h)
+
+
+class Converter(_WindowStream):
+    """fldr_shutter: host frames (tuples of numpy planes) pushed one by one at in_rate; each push returns the output frames at out_rate
+    whose exposure window it completes (schedule()), flush() the one still open."""
+
+    def __init__(self, native_model, H, W, fmt=None, in_rate=120, out_rate=24, shutter=(1, 2), sub=1, scene=True, params=None):
+        fmt = fmt or Format()
+        self._open(native_model, config(in_rate, out_rate, shutter, sub, H, W, fmt, native_model.device.index or 0, scene, params), H, W, fmt)

@@ -1,7 +1,8 @@
 // libfldr_light.so, host side: the curve object and its tables, validation, accumulate / resolve / mix through the video library's
 // converters (../video/video_kernels.hip is compiled into this library as shared text, the way frame_host.h is), fldr_light_forward on
 // the planar frames fldr_video_forward leaves in its workspace, and the converter — the planner and session of
-// ../shutter/session_host.h handed this library's three integration calls.  The only fldr_* functions called are those of fldr_shutter.h,
+// ../shutter/session_host.h handed this library's three integration calls, with the checks of sources, blocks and the forward's
+// refusals that header shares with libfldr_shutter.so.  The only fldr_* functions called are those of fldr_shutter.h,
 // fldr_rate.h, fldr_video.h and fldr_model.h.
 #include <hip/hip_runtime.h>
 
@@ -83,19 +84,6 @@ int plan_of(int H, int W, const fldr_video_format* fmt, Plan& p) {
     return 0;
 }
 
-int check_sources(const Plan& p, const fldr_video_frame* frames, const int32_t* weights, int n) {
-    if (!frames || !weights || n < 1) return FLDR_LIGHT_E_ARG;
-    for (int k = 0; k < n; ++k) CK(check_frame(frames[k], p.fmt, p.W));
-    int64_t total = 0;
-    for (int k = 0; k < n; ++k) {
-        if (weights[k] < 1 || weights[k] > 255) return FLDR_LIGHT_E_WEIGHT;
-        total += weights[k];
-    }
-    return total > FLDR_LIGHT_MAX_TOTAL ? FLDR_LIGHT_E_WEIGHT : 0;
-}
-
-int check_block(const void* p) { return !p || ((uintptr_t)p & (ALIGN - 1)) ? FLDR_LIGHT_E_ACC : 0; }
-
 // the curve is looked at last of the host-only checks: every other defect of a call is reported whatever the curve
 int check_curve(const fldr_light_curve* c, const fldr_video_format& fmt) {
     if (!c) return FLDR_LIGHT_E_ARG;
@@ -168,10 +156,6 @@ int enqueue_mix(const Plan& p, const fldr_light_curve* c, const fldr_video_frame
     src.n = n;
     CK(launch_mix(p.deep, p.count, tables_of(c), src, (uint32_t)total, planar, aligned16(src), s));
     return from_planar(p, planar, out, s);
-}
-
-bool same_format(const fldr_video_format& a, const fldr_video_format& b) {
-    return a.layout == b.layout && a.matrix == b.matrix && a.range == b.range && deep(a) == deep(b);
 }
 
 }  // namespace
@@ -258,9 +242,9 @@ extern "C" FLDR_LIGHT_API int fldr_light_accumulate(int H, int W, const fldr_vid
                                                     void* scratch, void* stream) {
     Plan p;
     CK(plan_of(H, W, fmt, p));
-    CK(check_sources(p, frames, weights, n));
-    CK(check_block(acc));
-    CK(check_block(scratch));
+    CK(check_sources(p.fmt, W, frames, weights, n, FLDR_LIGHT_E_ARG, FLDR_LIGHT_E_WEIGHT, FLDR_LIGHT_MAX_TOTAL));
+    CK(check_aligned(acc, FLDR_LIGHT_E_ACC));
+    CK(check_aligned(scratch, FLDR_LIGHT_E_ACC));
     CK(check_curve(curve, p.fmt));
     return enqueue_accumulate(p, curve, frames, weights, n, first != 0, acc, scratch, (hipStream_t)stream);
 }
@@ -272,8 +256,8 @@ extern "C" FLDR_LIGHT_API int fldr_light_resolve(int H, int W, const fldr_video_
     if (!out) return FLDR_LIGHT_E_ARG;
     CK(check_frame(*out, p.fmt, W));
     if (total < 1 || total > FLDR_LIGHT_MAX_TOTAL) return FLDR_LIGHT_E_WEIGHT;
-    CK(check_block(acc));
-    CK(check_block(scratch));
+    CK(check_aligned(acc, FLDR_LIGHT_E_ACC));
+    CK(check_aligned(scratch, FLDR_LIGHT_E_ACC));
     CK(check_curve(curve, p.fmt));
     return enqueue_resolve(p, curve, acc, total, *out, scratch, (hipStream_t)stream);
 }
@@ -284,9 +268,9 @@ extern "C" FLDR_LIGHT_API int fldr_light_mix(int H, int W, const fldr_video_form
     Plan p;
     CK(plan_of(H, W, fmt, p));
     if (n > MAX_FRAMES || !out) return FLDR_LIGHT_E_ARG;
-    CK(check_sources(p, frames, weights, n));
+    CK(check_sources(p.fmt, W, frames, weights, n, FLDR_LIGHT_E_ARG, FLDR_LIGHT_E_WEIGHT, FLDR_LIGHT_MAX_TOTAL));
     CK(check_frame(*out, p.fmt, W));
-    CK(check_block(scratch));
+    CK(check_aligned(scratch, FLDR_LIGHT_E_ACC));
     CK(check_curve(curve, p.fmt));
     return enqueue_mix(p, curve, frames, weights, n, *out, scratch, (hipStream_t)stream);
 }
@@ -315,23 +299,10 @@ extern "C" FLDR_LIGHT_API int64_t fldr_light_workspace_bytes(const fldr_model* m
 extern "C" FLDR_LIGHT_API int fldr_light_forward(const fldr_model* m, const fldr_video_io* io, const fldr_light_curve* curve, int w0, int w1,
                                                  const int32_t* w, void* ws, int64_t ws_bytes, void* stream) {
     // everything fldr_video_forward and the mix would refuse is refused here, before anything is enqueued
-    if (!io || !w) return FLDR_LIGHT_E_ARG;
-    if (io->H < 2 || io->W < 2 || io->n_t < 1 || !io->t || !io->out) return FLDR_VIDEO_E_ARG;
-    if (io->n_t > FLDR_SHUTTER_MAX_SUB) return FLDR_LIGHT_E_ARG;
-    CK(check_format(io->in_format));
-    CK(check_format(io->out_format));
-    if (!same_format(io->in_format, io->out_format)) return FLDR_LIGHT_E_FORMAT;
+    int total;
+    CK(forward_preamble(io, w0, w1, w, FLDR_LIGHT_E_ARG, FLDR_LIGHT_E_FORMAT, FLDR_LIGHT_E_WEIGHT, FLDR_LIGHT_MAX_TOTAL, &total));
     const fldr_video_format& fmt = io->in_format;
     const int H = io->H, W = io->W, n_t = io->n_t;
-    for (int f = 0; f < 2; ++f) CK(check_frame(io->in[f], fmt, W));
-    CK(check_frame(io->out[0], fmt, W));
-    if (w0 < 0 || w0 > 255 || w1 < 0 || w1 > 255) return FLDR_LIGHT_E_WEIGHT;
-    int total = w0 + w1;
-    for (int k = 0; k < n_t; ++k) {
-        if (w[k] < 1 || w[k] > 255) return FLDR_LIGHT_E_WEIGHT;
-        total += w[k];
-    }
-    if (total > FLDR_LIGHT_MAX_TOTAL) return FLDR_LIGHT_E_WEIGHT;
     Plan p;
     CK(plan_of(H, W, &fmt, p));
     CK(check_curve(curve, fmt));

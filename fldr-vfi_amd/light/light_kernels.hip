@@ -7,7 +7,8 @@
 // and written once for all the frames of a launch.  The wide form (VEC) loads the 16 bytes at once and needs every source address
 // 16-byte aligned; the per-sample form does the same arithmetic on loads of one sample each (the second frame of a planar pair of odd
 // size starts anywhere).  Accumulator and output are the library's own buffers and always aligned.  The samples behind the last whole 16
-// bytes go one by one in either form.
+// bytes go one by one in either form.  The 16-byte reader, the weighted gather over the frames (here with lin[] as the per-sample map),
+// the accumulator's uint4 form and the launch by VEC are ../video/sample16_device.h, one text with the shutter kernels.
 //
 // Both tables of the curve live in LDS, copied by every workgroup before its first item: lin[code] (up to 4 KB) for the way in, and for
 // the way back up[c] = (mid[c] + 1) >> 1 (up to 4 KB).  With T the total and X = 2 acc + T the header's q is X / (2 T), and
@@ -19,9 +20,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../video/sample16_device.h"
 #include "light_internal.h"
 
 namespace fldr_light_impl {
+
+using fldr_sample16::load_acc;
+using fldr_sample16::store_acc;
 
 #define LK_THREADS 256
 #define LK_MAX_BLOCKS 2048       // 8 workgroups per CU of an MI355X; longer frames walk with the grid's stride
@@ -38,52 +43,11 @@ template <bool DEEP> __device__ __forceinline__ uint32_t code_at(const void* bas
     return reinterpret_cast<const uint8_t*>(base)[i];
 }
 
-// 16 bytes at p -> four dwords; !VEC: from loads of one sample each (p is then only sample-aligned)
-template <bool DEEP, bool VEC> __device__ __forceinline__ void load16(const uint8_t* p, uint32_t d[4]) {
-    if (VEC) {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    } else if (!DEEP) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            d[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
-    } else {
-        const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d[i] = (uint32_t)q[2 * i] | ((uint32_t)q[2 * i + 1] << 16);
-    }
-}
-
-// s += w * lin[code] for the samples in four dwords
-template <bool DEEP> __device__ __forceinline__ void add16(uint32_t* s, const uint32_t d[4], uint32_t w, const uint32_t* lin) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (!DEEP) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s[4 * i + j] += w * lin[(d[i] >> (8 * j)) & 0xffu];
-        } else {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) s[2 * i + j] += w * lin[(d[i] >> (16 * j)) & 0x3ffu];
-        }
-    }
-}
-
-// the weighted linear sum of the 16 bytes at byte offset `off` of every frame, added to s; four frames' loads in flight
+// the weighted linear sum of the 16 bytes at byte offset `off` of every frame, added to s (../video/sample16_device.h)
 template <bool DEEP, bool VEC>
 __device__ __forceinline__ void gather16(const Sources& a, int64_t off, uint32_t* s, const uint32_t* lin) {
-    int k0 = 0;
-    for (; k0 + 4 <= a.n; k0 += 4) {
-        uint32_t d[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) load16<DEEP, VEC>(reinterpret_cast<const uint8_t*>(a.codes[k0 + u]) + off, d[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) add16<DEEP>(s, d[u], a.weight[k0 + u], lin);
-    }
-    for (; k0 < a.n; ++k0) {
-        uint32_t d[4];
-        load16<DEEP, VEC>(reinterpret_cast<const uint8_t*>(a.codes[k0]) + off, d);
-        add16<DEEP>(s, d, a.weight[k0], lin);
-    }
+    fldr_sample16::gather16<DEEP, 0, VEC>(
+        a.n, a.weight, [&](int k) { return reinterpret_cast<const uint8_t*>(a.codes[k]) + off; }, [&](uint32_t code) { return lin[code]; }, s);
 }
 
 template <bool DEEP> __device__ __forceinline__ uint32_t gather1(const Sources& a, int64_t i, const uint32_t* lin) {
@@ -120,14 +84,6 @@ template <bool DEEP> __device__ __forceinline__ void store_code(void* base, int6
     else reinterpret_cast<uint8_t*>(base)[i] = (uint8_t)v;
 }
 
-template <int SPC> __device__ __forceinline__ void load_acc(const uint32_t* ap, uint32_t* s) {
-#pragma unroll
-    for (int i = 0; i < SPC / 4; ++i) {
-        const uint4 v = reinterpret_cast<const uint4*>(ap)[i];
-        s[4 * i] = v.x; s[4 * i + 1] = v.y; s[4 * i + 2] = v.z; s[4 * i + 3] = v.w;
-    }
-}
-
 template <bool DEEP> __device__ __forceinline__ void stage_lin(uint32_t* lin, const Tables& t) {
     for (int i = threadIdx.x; i < Form<DEEP>::CODES; i += LK_THREADS) lin[i] = t.lin[i];
 }
@@ -159,8 +115,7 @@ __global__ __launch_bounds__(LK_THREADS) void light_accumulate_kernel(Tables t, 
             load_acc<SPC>(ap, s);
         }
         gather16<DEEP, VEC>(a, 16ll * item, s, lin);
-#pragma unroll
-        for (int i = 0; i < SPC / 4; ++i) reinterpret_cast<uint4*>(ap)[i] = make_uint4(s[4 * i], s[4 * i + 1], s[4 * i + 2], s[4 * i + 3]);
+        store_acc<SPC>(ap, s);
     }
     LK_TAIL() {
         const int64_t i = (int64_t)full * SPC + threadIdx.x;
@@ -220,10 +175,8 @@ dim3 grid_of(bool deep, int64_t count) {
 int launch_accumulate(bool deep, int64_t count, const Tables& t, const Sources& src, bool first, uint32_t* acc, bool vec, hipStream_t stream) {
     const dim3 grid = grid_of(deep, count);
     const int f = first ? 1 : 0;
-    if (deep) { if (vec) light_accumulate_kernel<true, true><<<grid, LK_THREADS, 0, stream>>>(t, src, acc, count, f);
-                else light_accumulate_kernel<true, false><<<grid, LK_THREADS, 0, stream>>>(t, src, acc, count, f); }
-    else { if (vec) light_accumulate_kernel<false, true><<<grid, LK_THREADS, 0, stream>>>(t, src, acc, count, f);
-           else light_accumulate_kernel<false, false><<<grid, LK_THREADS, 0, stream>>>(t, src, acc, count, f); }
+    if (deep) SAMPLE16_LAUNCH_VEC(light_accumulate_kernel, true, vec, grid, LK_THREADS, stream, t, src, acc, count, f);
+    else SAMPLE16_LAUNCH_VEC(light_accumulate_kernel, false, vec, grid, LK_THREADS, stream, t, src, acc, count, f);
     return (int)hipGetLastError();
 }
 
@@ -236,10 +189,8 @@ int launch_resolve(bool deep, int64_t count, const Tables& t, const uint32_t* ac
 
 int launch_mix(bool deep, int64_t count, const Tables& t, const Sources& src, uint32_t total, void* out, bool vec, hipStream_t stream) {
     const dim3 grid = grid_of(deep, count);
-    if (deep) { if (vec) light_mix_kernel<true, true><<<grid, LK_THREADS, 0, stream>>>(t, src, total, out, count);
-                else light_mix_kernel<true, false><<<grid, LK_THREADS, 0, stream>>>(t, src, total, out, count); }
-    else { if (vec) light_mix_kernel<false, true><<<grid, LK_THREADS, 0, stream>>>(t, src, total, out, count);
-           else light_mix_kernel<false, false><<<grid, LK_THREADS, 0, stream>>>(t, src, total, out, count); }
+    if (deep) SAMPLE16_LAUNCH_VEC(light_mix_kernel, true, vec, grid, LK_THREADS, stream, t, src, total, out, count);
+    else SAMPLE16_LAUNCH_VEC(light_mix_kernel, false, vec, grid, LK_THREADS, stream, t, src, total, out, count);
     return (int)hipGetLastError();
 }
 

@@ -76,8 +76,8 @@ __global__ __launch_bounds__(SK_THREADS) void scene_accumulate_kernel(MeasureArg
         const uint8_t* p1 = a.y[1] + (int64_t)row * a.pitch[1] + off;
         if (nbytes == 16) {
             uint32_t d0[4], d1[4];
-            load16<MODE, VEC>(p0, d0);
-            load16<MODE, VEC>(p1, d1);
+            load16<MODE != Y8_BYTE, VEC>(p0, d0);
+            load16<MODE != Y8_BYTE, VEC>(p1, d1);
             bool same = true;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -140,7 +140,7 @@ int scene_measure(const void* y0, int64_t pitch0, const void* y1, int64_t pitch1
     const bool vec = luma_vec_ok(y0, pitch0, y1, pitch1);
     const uint32_t blocks = min((a.items + SK_THREADS - 1) / SK_THREADS, (uint32_t)SK_MAX_BLOCKS);
     scene_zero_kernel<<<1, SK_THREADS, 0, stream>>>(a.state);
-    LUMA8_LAUNCH(scene_accumulate_kernel, mode, vec, blocks, SK_THREADS, stream, a);
+    SAMPLE16_LAUNCH(scene_accumulate_kernel, mode, vec, blocks, SK_THREADS, stream, a);
     scene_decide_kernel<<<1, SK_THREADS, 0, stream>>>(a.state, H, W, sad_permille, hist_permille);
     return (int)hipGetLastError();
 }

@@ -1,7 +1,9 @@
 // The window rule and the converter of include/fldr_shutter.h: which grid points an output keeps, which push returns it, the one forward
 // of a push and the windows on one accumulator.  Included by shutter_host.hip and by ../light/light_host.hip: libfldr_light.so plans exactly
 // as libfldr_shutter.so because both compile this text.  How points are summed and resolved is the including library's: a small struct of
-// integration operations (Integration).  Everything is in the unnamed namespace: nothing here becomes a symbol of either library.
+// integration operations (Integration).  What the kernel entry points and the forward of both libraries check alike is here too, each
+// taking the including library's codes: same_format, check_aligned, check_sources and forward_preamble.  Everything is in the unnamed
+// namespace: nothing here becomes a symbol of either library.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +31,48 @@ struct Integration {
     int (*mix)(void* ctx, int H, int W, const fldr_video_format& fmt, const fldr_video_frame* frames, const int32_t* weights, int n,
                const fldr_video_frame& out, void* scratch, hipStream_t s);
 };
+
+// ---- what accumulate / resolve / mix and the forward of either library refuse alike ----
+bool same_format(const fldr_video_format& a, const fldr_video_format& b) {
+    return a.layout == b.layout && a.matrix == b.matrix && a.range == b.range && deep(a) == deep(b);
+}
+
+// an accumulator or scratch block: present and ALIGN-aligned, else the caller's code
+int check_aligned(const void* p, int code) { return !p || ((uintptr_t)p & (ALIGN - 1)) ? code : 0; }
+
+// frames present, every frame valid for the format, every weight in 1 .. 255, and their total <= max_total (0: no bound)
+int check_sources(const fldr_video_format& fmt, int W, const fldr_video_frame* frames, const int32_t* weights, int n, int e_arg, int e_weight,
+                  int64_t max_total) {
+    if (!frames || !weights || n < 1) return e_arg;
+    for (int k = 0; k < n; ++k) CK(check_frame(frames[k], fmt, W));
+    int64_t total = 0;
+    for (int k = 0; k < n; ++k) {
+        if (weights[k] < 1 || weights[k] > 255) return e_weight;
+        total += weights[k];
+    }
+    return max_total && total > max_total ? e_weight : 0;
+}
+
+// What a forward refuses before it looks at its own geometry, in the order fldr_shutter_forward and fldr_light_forward document: everything
+// fldr_video_forward and the mix would refuse about io and the weights.  max_total as in check_sources; *total = w0 + w1 + the sum of w.
+int forward_preamble(const fldr_video_io* io, int w0, int w1, const int32_t* w, int e_arg, int e_format, int e_weight, int64_t max_total,
+                     int* total) {
+    if (!io || !w) return e_arg;
+    if (io->H < 2 || io->W < 2 || io->n_t < 1 || !io->t || !io->out) return FLDR_VIDEO_E_ARG;
+    if (io->n_t > FLDR_SHUTTER_MAX_SUB) return e_arg;
+    CK(check_format(io->in_format));
+    CK(check_format(io->out_format));
+    if (!same_format(io->in_format, io->out_format)) return e_format;
+    for (int f = 0; f < 2; ++f) CK(check_frame(io->in[f], io->in_format, io->W));
+    CK(check_frame(io->out[0], io->in_format, io->W));
+    if (w0 < 0 || w0 > 255 || w1 < 0 || w1 > 255) return e_weight;
+    *total = w0 + w1;
+    for (int k = 0; k < io->n_t; ++k) {
+        if (w[k] < 1 || w[k] > 255) return e_weight;
+        *total += w[k];
+    }
+    return max_total && *total > max_total ? e_weight : 0;
+}
 
 typedef __int128 wide;                 // the window rule's products: exact whatever j is
 

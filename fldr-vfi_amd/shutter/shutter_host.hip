@@ -1,6 +1,7 @@
 // libfldr_shutter.so, host side: validation, accumulate / resolve / mix, fldr_shutter_forward (fldr_video_forward -> mix), and the public
 // face of the window rule (fldr_shutter_plan) and of the shutter converter for streams of host frames.  The rule and the converter
-// themselves are in session_host.h (shared with libfldr_light.so), which this file hands its three integration calls; the video API's
+// themselves are in session_host.h (shared with libfldr_light.so, with the checks both libraries make alike: the sources, the alignment
+// of a block, the forward's refusals), which this file hands its three integration calls; the video API's
 // rules for formats and frames, and the stream / device block / pinned block the converter owns, come from ../video/frame_host.h.  The
 // only fldr_* functions called are those of fldr_rate.h, fldr_video.h and fldr_model.h.
 #include <hip/hip_runtime.h>
@@ -17,10 +18,6 @@ using namespace fldr_shutter_impl;
 
 namespace {
 
-bool same_format(const fldr_video_format& a, const fldr_video_format& b) {
-    return a.layout == b.layout && a.matrix == b.matrix && a.range == b.range && deep(a) == deep(b);
-}
-
 bool aligned16(const fldr_video_frame& f, int np) {
     uintptr_t bits = 0;
     for (int p = 0; p < np; ++p) bits |= (uintptr_t)f.plane[p] | (uintptr_t)f.pitch[p];
@@ -32,15 +29,6 @@ int check_size(int H, int W, const fldr_video_format* fmt, Geometry& g) {
     CK(check_format(*fmt));
     return geometry(H, W, *fmt, g) ? 0 : FLDR_SHUTTER_E_ARG;
 }
-
-int check_sources(const fldr_video_format& fmt, int W, const fldr_video_frame* frames, const int32_t* weights, int n) {
-    if (!frames || !weights || n < 1) return FLDR_SHUTTER_E_ARG;
-    for (int k = 0; k < n; ++k) CK(check_frame(frames[k], fmt, W));
-    for (int k = 0; k < n; ++k) if (weights[k] < 1 || weights[k] > 255) return FLDR_SHUTTER_E_WEIGHT;
-    return 0;
-}
-
-int check_acc(const void* acc) { return !acc || ((uintptr_t)acc & (ALIGN - 1)) ? FLDR_SHUTTER_E_ACC : 0; }
 
 // frames[k0 .. k0 + n) as one launch reads them; -> whether all of them take the wide form
 bool fill_sources(Sources& s, const Geometry& g, const fldr_video_frame* frames, const int32_t* weights, int n) {
@@ -162,8 +150,8 @@ extern "C" FLDR_SHUTTER_API int fldr_shutter_accumulate(int H, int W, const fldr
                                                         const int32_t* weights, int n, int first, void* acc, void* stream) {
     Geometry g;
     CK(check_size(H, W, fmt, g));
-    CK(check_sources(*fmt, W, frames, weights, n));
-    CK(check_acc(acc));
+    CK(check_sources(*fmt, W, frames, weights, n, FLDR_SHUTTER_E_ARG, FLDR_SHUTTER_E_WEIGHT, 0));
+    CK(check_aligned(acc, FLDR_SHUTTER_E_ACC));
     return enqueue_accumulate(g, frames, weights, n, first != 0, acc, (hipStream_t)stream);
 }
 
@@ -174,7 +162,7 @@ extern "C" FLDR_SHUTTER_API int fldr_shutter_resolve(int H, int W, const fldr_vi
     if (!out) return FLDR_SHUTTER_E_ARG;
     CK(check_frame(*out, *fmt, W));
     if (total < 1 || total > FLDR_SHUTTER_MAX_TOTAL) return FLDR_SHUTTER_E_WEIGHT;
-    CK(check_acc(acc));
+    CK(check_aligned(acc, FLDR_SHUTTER_E_ACC));
     return enqueue_resolve(g, acc, total, *out, (hipStream_t)stream);
 }
 
@@ -183,7 +171,7 @@ extern "C" FLDR_SHUTTER_API int fldr_shutter_mix(int H, int W, const fldr_video_
     Geometry g;
     CK(check_size(H, W, fmt, g));
     if (n > MAX_FRAMES || !out) return FLDR_SHUTTER_E_ARG;
-    CK(check_sources(*fmt, W, frames, weights, n));
+    CK(check_sources(*fmt, W, frames, weights, n, FLDR_SHUTTER_E_ARG, FLDR_SHUTTER_E_WEIGHT, 0));
     CK(check_frame(*out, *fmt, W));
     return enqueue_mix(g, frames, weights, n, *out, (hipStream_t)stream);
 }
@@ -213,18 +201,10 @@ extern "C" FLDR_SHUTTER_API int64_t fldr_shutter_workspace_bytes(const fldr_mode
 extern "C" FLDR_SHUTTER_API int fldr_shutter_forward(const fldr_model* m, const fldr_video_io* io, int w0, int w1, const int32_t* w, void* ws,
                                                      int64_t ws_bytes, void* stream) {
     // everything fldr_video_forward and the mix would refuse is refused here, before anything is enqueued
-    if (!io || !w) return FLDR_SHUTTER_E_ARG;
-    if (io->H < 2 || io->W < 2 || io->n_t < 1 || !io->t || !io->out) return FLDR_VIDEO_E_ARG;
-    if (io->n_t > FLDR_SHUTTER_MAX_SUB) return FLDR_SHUTTER_E_ARG;
-    CK(check_format(io->in_format));
-    CK(check_format(io->out_format));
-    if (!same_format(io->in_format, io->out_format)) return FLDR_SHUTTER_E_FORMAT;
+    int total;
+    CK(forward_preamble(io, w0, w1, w, FLDR_SHUTTER_E_ARG, FLDR_SHUTTER_E_FORMAT, FLDR_SHUTTER_E_WEIGHT, 0, &total));
     const fldr_video_format& fmt = io->in_format;
     const int H = io->H, W = io->W, n_t = io->n_t;
-    for (int f = 0; f < 2; ++f) CK(check_frame(io->in[f], fmt, W));
-    CK(check_frame(io->out[0], fmt, W));
-    if (w0 < 0 || w0 > 255 || w1 < 0 || w1 > 255) return FLDR_SHUTTER_E_WEIGHT;
-    for (int k = 0; k < n_t; ++k) if (w[k] < 1 || w[k] > 255) return FLDR_SHUTTER_E_WEIGHT;
     Geometry g;
     if (!geometry(H, W, fmt, g)) return FLDR_SHUTTER_E_ARG;
     const int64_t vb = fldr_video_workspace_bytes(m, H, W, n_t);

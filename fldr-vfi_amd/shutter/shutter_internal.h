@@ -3,14 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../video/sample16_device.h"
 #include "fldr_shutter.h"
 
 namespace fldr_shutter_impl {
 
 // how the value sits in a sample
-enum { S_BYTE = 0,                     // depth 8: the byte
-       S_P010 = 1,                     // word >> 6, written as v << 6
-       S_LOW10 = 2 };                  // word & 0x3ff, written as v
+enum { S_BYTE = fldr_sample16::FORM_BYTE,        // depth 8: the byte
+       S_P010 = fldr_sample16::FORM_P010,        // word >> 6, written as v << 6
+       S_LOW10 = fldr_sample16::FORM_LOW10 };    // word & 0x3ff, written as v
 
 constexpr int MAX_FRAMES = FLDR_SHUTTER_LAUNCH_FRAMES;
 

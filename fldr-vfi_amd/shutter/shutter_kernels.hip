@@ -7,13 +7,17 @@
 // and needs every plane address and pitch involved 16-byte aligned; the per-sample form does the same arithmetic on loads and stores of
 // one sample each.  The samples of a row behind its last whole 16 bytes go one by one in either form.  The plane is the grid's y, so
 // everything read from the kernel arguments is uniform.  Every quantity is an integer below 2^32 (shutter_internal.h, fldr_shutter.h),
-// so the order of the frames and the shape of the launch do not show in the result.
+// so the order of the frames and the shape of the launch do not show in the result.  The 16-byte reader, the weighted gather over the
+// frames, the accumulator's uint4 form and the launch by sample form are ../video/sample16_device.h, one text with the light kernels.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "shutter_internal.h"
 
 namespace fldr_shutter_impl {
+
+using fldr_sample16::load_acc;
+using fldr_sample16::store_acc;
 
 #define TK_THREADS 256
 #define TK_MAX_BLOCKS 2048       // 8 workgroups per CU of an MI355X; larger planes walk with the grid's stride
@@ -34,52 +38,11 @@ template <int MODE> __device__ __forceinline__ void store_sample(uint8_t* p, uin
     else *reinterpret_cast<uint16_t*>(p) = (uint16_t)(MODE == S_P010 ? (v << 6) : v);
 }
 
-// 16 bytes at p -> four dwords; !VEC: from loads of one sample each (p is then only sample-aligned)
-template <int MODE, bool VEC> __device__ __forceinline__ void load16(const uint8_t* p, uint32_t d[4]) {
-    if (VEC) {
-        const uint4 v = *reinterpret_cast<const uint4*>(p);
-        d[0] = v.x; d[1] = v.y; d[2] = v.z; d[3] = v.w;
-    } else if (MODE == S_BYTE) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            d[i] = (uint32_t)p[4 * i] | ((uint32_t)p[4 * i + 1] << 8) | ((uint32_t)p[4 * i + 2] << 16) | ((uint32_t)p[4 * i + 3] << 24);
-    } else {
-        const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d[i] = (uint32_t)q[2 * i] | ((uint32_t)q[2 * i + 1] << 16);
-    }
-}
-
-// s += w * the values of the samples in four dwords
-template <int MODE> __device__ __forceinline__ void add16(uint32_t* s, const uint32_t d[4], uint32_t w) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        if (MODE == S_BYTE) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) s[4 * i + j] += w * ((d[i] >> (8 * j)) & 0xffu);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 2; ++j) s[2 * i + j] += w * ((d[i] >> (16 * j + (MODE == S_P010 ? 6 : 0))) & 0x3ffu);
-        }
-    }
-}
-
-// the weighted sum of 16 bytes at (row, off) of plane p of every frame, added to s; four frames' loads in flight
+// the weighted sum of 16 bytes at (row, off) of plane p of every frame, added to s (../video/sample16_device.h)
 template <int MODE, bool VEC>
 __device__ __forceinline__ void gather16(const Sources& a, int p, uint32_t row, int64_t off, uint32_t* s) {
-    int k0 = 0;
-    for (; k0 + 4 <= a.n; k0 += 4) {
-        uint32_t d[4][4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) load16<MODE, VEC>(a.plane[k0 + u][p] + (int64_t)row * a.pitch[k0 + u][p] + off, d[u]);
-#pragma unroll
-        for (int u = 0; u < 4; ++u) add16<MODE>(s, d[u], a.weight[k0 + u]);
-    }
-    for (; k0 < a.n; ++k0) {
-        uint32_t d[4];
-        load16<MODE, VEC>(a.plane[k0][p] + (int64_t)row * a.pitch[k0][p] + off, d);
-        add16<MODE>(s, d, a.weight[k0]);
-    }
+    fldr_sample16::gather16<MODE != S_BYTE, MODE == S_P010 ? 6 : 0, VEC>(
+        a.n, a.weight, [&](int k) { return a.plane[k][p] + (int64_t)row * a.pitch[k][p] + off; }, [](uint32_t v) { return v; }, s);
 }
 
 template <int MODE> __device__ __forceinline__ uint32_t gather1(const Sources& a, int p, uint32_t row, int64_t off) {
@@ -112,14 +75,6 @@ template <int MODE, bool VEC> __device__ __forceinline__ void finish16(const uin
     }
 }
 
-template <int SPC> __device__ __forceinline__ void load_acc(const uint32_t* ap, uint32_t* s) {
-#pragma unroll
-    for (int i = 0; i < SPC / 4; ++i) {
-        const uint4 v = reinterpret_cast<const uint4*>(ap)[i];
-        s[4 * i] = v.x; s[4 * i + 1] = v.y; s[4 * i + 2] = v.z; s[4 * i + 3] = v.w;
-    }
-}
-
 // One item is one 16-byte group of a row of plane p = blockIdx.y, the row's partial last group included.
 #define TK_WALK(g)                                                                                                   \
     const int p = blockIdx.y;                                                                                        \
@@ -147,8 +102,7 @@ __global__ __launch_bounds__(TK_THREADS) void shutter_accumulate_kernel(Geometry
                 load_acc<SPC>(ap, s);
             }
             gather16<MODE, VEC>(a, p, row, off, s);
-#pragma unroll
-            for (int i = 0; i < SPC / 4; ++i) reinterpret_cast<uint4*>(ap)[i] = make_uint4(s[4 * i], s[4 * i + 1], s[4 * i + 2], s[4 * i + 3]);
+            store_acc<SPC>(ap, s);
         } else {
             uint32_t* ap = acc + g.acc_tail[p] + (int64_t)row * tail;
             for (int i = 0; i < tail; ++i) ap[i] = (first ? 0u : ap[i]) + gather1<MODE>(a, p, row, off + i * BPS);
@@ -242,28 +196,19 @@ dim3 grid_of(const Geometry& g) {
 
 }  // namespace
 
-#define TK_LAUNCH(KERNEL, ...)                                                                                              \
-    do {                                                                                                                    \
-        const dim3 grid = grid_of(g);                                                                                       \
-        if (g.mode == S_BYTE) { if (vec) KERNEL<S_BYTE, true><<<grid, TK_THREADS, 0, stream>>>(__VA_ARGS__);                \
-                                else KERNEL<S_BYTE, false><<<grid, TK_THREADS, 0, stream>>>(__VA_ARGS__); }                 \
-        else if (g.mode == S_P010) { if (vec) KERNEL<S_P010, true><<<grid, TK_THREADS, 0, stream>>>(__VA_ARGS__);           \
-                                     else KERNEL<S_P010, false><<<grid, TK_THREADS, 0, stream>>>(__VA_ARGS__); }            \
-        else { if (vec) KERNEL<S_LOW10, true><<<grid, TK_THREADS, 0, stream>>>(__VA_ARGS__);                                \
-               else KERNEL<S_LOW10, false><<<grid, TK_THREADS, 0, stream>>>(__VA_ARGS__); }                                 \
-        return (int)hipGetLastError();                                                                                      \
-    } while (0)
-
 int launch_accumulate(const Geometry& g, const Sources& src, bool first, uint32_t* acc, bool vec, hipStream_t stream) {
-    TK_LAUNCH(shutter_accumulate_kernel, g, src, acc, first ? 1 : 0);
+    SAMPLE16_LAUNCH(shutter_accumulate_kernel, g.mode, vec, grid_of(g), TK_THREADS, stream, g, src, acc, first ? 1 : 0);
+    return (int)hipGetLastError();
 }
 
 int launch_resolve(const Geometry& g, const uint32_t* acc, const Target& dst, bool vec, hipStream_t stream) {
-    TK_LAUNCH(shutter_resolve_kernel, g, acc, dst);
+    SAMPLE16_LAUNCH(shutter_resolve_kernel, g.mode, vec, grid_of(g), TK_THREADS, stream, g, acc, dst);
+    return (int)hipGetLastError();
 }
 
 int launch_mix(const Geometry& g, const Sources& src, const Target& dst, bool vec, hipStream_t stream) {
-    TK_LAUNCH(shutter_mix_kernel, g, src, dst);
+    SAMPLE16_LAUNCH(shutter_mix_kernel, g.mode, vec, grid_of(g), TK_THREADS, stream, g, src, dst);
+    return (int)hipGetLastError();
 }
 
 }  // namespace fldr_shutter_impl
