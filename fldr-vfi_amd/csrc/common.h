@@ -278,7 +278,11 @@ __device__ __forceinline__ float fldr_tap_sample_p(const FldrTapP& p, const floa
 // ---- F.interpolate(bilinear, align_corners=False) source index / lambda -------------------------
 __device__ __forceinline__ void fldr_lin_src(int o, float scale, int in_size, int& i0, int& i1, float& l1) {
 #pragma clang fp contract(off)
-    float r = scale * ((float)o + 0.5f) - 0.5f;
+    // ONE rounding, as the reference forms it: PyTorch's scale * (o + 0.5) - 0.5 is compiled to a fused multiply-add (its CPU and CUDA
+    // builds alike).  With the product rounded on its own the position is off by up to an ulp of the coordinate wherever the scale is
+    // no power of two — 9 -> 5 rows, x3: 2.6e-6 from fp32 torch, 3.1e-6 from float64 where torch is at 1.2e-6; fused: 3e-8 from torch
+    // (tests/test_gpu_warp_ops.py).  The model's scales (1/2, 1/8) are powers of two: exact either way, the same bits as before.
+    float r = __builtin_fmaf(scale, (float)o + 0.5f, -0.5f);
     r = r < 0.0f ? 0.0f : r;
     int i = (int)r;
     i0 = i < in_size - 1 ? i : in_size - 1;

@@ -2115,8 +2115,9 @@ def test_odd_shape_stress_of_kernel_variants(hip, dev, capsys, hooks):
 
 
 def test_operators_random_odd_shapes_vs_oracle(hip, oracle, dev):
-    """Correlation (forward / backward), raw splat (forward / backward), bwarp and resize on random odd shapes — single
-    rows / columns, sizes that are not multiples of the 8x32 / 64x4 tiles, several samples — against the oracle."""
+    """Correlation (forward / backward) and the raw splat (forward / backward) on random odd shapes — single rows / columns,
+    sizes that are not multiples of the 8x32 / 64x4 tiles, several samples — against the oracle.  The backward warp, the splat
+    metric and the resizes at such shapes: tests/test_gpu_warp_ops.py."""
     import random
     from OpticalFlow import correlation
     rnd = random.Random(7)
