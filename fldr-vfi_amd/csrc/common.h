@@ -38,8 +38,11 @@ static inline int fldr_set_max_lds(const void* fn, int bytes, std::atomic<uint64
 }
 
 // ---- fp16 hi/lo split with a range guard ---------------------------------------------------------------------------
-// x = hi + lo, hi = x truncated to 11 significant bits (exact in fp16), lo = fp16(x - hi): the operand form of the
-// 3 x fp16-split MFMA convolutions.  fp16 ends at 65504: beyond it a plain conversion gives hi = inf and the convolution
+// x = hi + lo, hi = x truncated to 11 significant bits (exact in fp16 from |x| = 2^-14 up; below it the fp16 is subnormal and the
+// conversion rounds the truncated value to a multiple of 2^-24), lo = fp16(x - t) with t the fp32 truncation, not float(hi): the operand
+// form of the 3 x fp16-split MFMA convolutions.  lo is itself subnormal below |x| = 0.25 (|x - t| < 2^-10 |x|), so the pair carries
+// 22 significant bits from 0.25 up and an absolute error of up to 2^-24 (1 + 2^-9) below it (tests/conv_float_ref.py).
+// fp16 ends at 65504: beyond it a plain conversion gives hi = inf and the convolution
 // NaN where the fp32 reference stays finite.  Guard: both halves are clamped to +-65504 (|x| < 131008 is then still
 // represented, to fp16 precision of the excess: absolute error <= 16; beyond that — and for NaN inputs — the value
 // SATURATES to a finite number) and the event is recorded in a sticky per-library flag that fldr_range_status()

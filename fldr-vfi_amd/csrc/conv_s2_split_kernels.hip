@@ -1410,6 +1410,7 @@ static int s2_split_run(const fldr_conv_desc* d, int out_rows, int src_rows, fld
     FLDR_CHECK_ARG(d->N > 0 && d->cin > 0 && d->cin <= 112 && d->cout > 0 && d->cout <= 64 && !d->residual);
     FLDR_CHECK_ARG(d->cout_store > 0 && d->cout_store <= d->cout && d->ksize == 4 && d->stride == 2);
     if (d->Hout != (d->Hin + 2 - 4) / 2 + 1 || d->Wout != (d->Win + 2 - 4) / 2 + 1) return FLDR_E_SHAPE;
+    if (d->Hin < 2 || d->Win < 2) return FLDR_E_SHAPE;             // no output row / column ((1 + 2 - 4) / 2 truncates to 0 above: the size is floor(-1 / 2) + 1 = 0)
     S2Args a;
     int csum = 0;
     for (int s = 0; s < FLDR_CONV_MAX_SRC; ++s) {
@@ -1493,6 +1494,7 @@ static int s2_spk_run(const fldr_conv_desc* d, const fldr_conv_desc* d2, int out
     FLDR_CHECK_ARG(d->cout_store > 0 && d->cout_store <= d->cout && d->ksize == 4 && d->stride == 2);
     if (d->Hout != (d->Hin + 2 - 4) / 2 + 1 || d->Wout != (d->Win + 2 - 4) / 2 + 1) return FLDR_E_SHAPE;
     if ((int64_t)d->Hin * d->Win * 16 >= (1ll << 32)) return FLDR_E_SHAPE;
+    if (d->Hin < 2 || d->Win < 2) return FLDR_E_SHAPE;             // no output row / column, as in s2_split_run
     S2Args a;
     for (int s = 0; s < FLDR_CONV_MAX_SRC; ++s) { a.src[s] = nullptr; a.src_bstride[s] = 0; a.src_cstride[s] = 0; a.src_cbegin[s] = 0; }
     a.src[0] = d->src[0]; a.src_bstride[0] = d->src_bstride[0]; a.src_cbegin[FLDR_CONV_MAX_SRC] = d->cin; a.n_src = 1;

@@ -1172,6 +1172,8 @@ class Spk:
 
 def _spk_alloc(N, C, H, W, device):
     nb = lib().fldr_spk_bytes(C, H, W)
+    if nb < 0:                  # an empty tensor (a stride-2 output of an input below 2 rows or columns): refused like every other bad shape
+        raise FldrError("no split-packed tensor of shape %s" % ((N, C, H, W),))
     return Spk(torch.empty(N * nb // 2, device=device, dtype=torch.float16), (N, C, H, W))
 
 

@@ -294,8 +294,9 @@ typedef struct fldr_conv_desc {
     float*       out;          /* [N,cout_store,Hout,Wout] */
     int32_t N, cin, cout, cout_store;
     int32_t Hin, Win;          /* input size (after any x2 upsampling) */
-    int32_t Hout, Wout;
-    int32_t ksize;             /* 3 (stride 1, pad 1) or 4 (stride 2, pad 1) */
+    int32_t Hout, Wout;        /* ksize 3: Hin, Win; ksize 4: (Hin - 2) / 2 + 1, (Win - 2) / 2 + 1 with Hin, Win >= 2 (FLDR_E_SHAPE below:
+                                  such an input has no output row / column) */
+    int32_t ksize;            /* 3 (stride 1, pad 1) or 4 (stride 2, pad 1) */
     int32_t stride;
     int32_t relu;
     int32_t precision;         /* 0: fp32 MFMA (exact fp32 products, default); 1: fp16 inputs, fp32 accumulate */
