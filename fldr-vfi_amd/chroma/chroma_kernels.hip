@@ -1,0 +1,325 @@
+// The kernels of libfldr_chroma.so: YUV 4:2:2 / 4:4:4 (planar, semiplanar, UYVY / YUYV; 8-bit bytes or 10-bit values in 16-bit words,
+// pitched planes) on either side of the model's planar BGR forward.  One input kernel and one output kernel, templated on the sample
+// type, the sampling and the layout.  All are bandwidth kernels: a thread owns a run of luma pixels along one row (16 at depth 8, 8 at
+// depth 10: 16 bytes of Y and of every BGR plane per lane); 4:2:2 has no vertical taps, so rows are independent.  Two forms of each:
+//   VEC      every plane pointer and pitch (and the planar BGR pointer) is 16-byte aligned and W is a multiple of the run: every plane
+//            is read and written with one or two 8- or 16-byte accesses per lane (planar 4:2:2 chroma: 8 bytes; everything else 16 or 32);
+//   !VEC     the same arithmetic on single samples, with the indices clamped into the row and the stores guarded.
+// The arithmetic is the colour definition of ../video/yuv_color.h in int32, exactly as tests/yuv_chroma_oracle.py states it.  Written with
+// h = 2 C for 4:4:4 (to BGR) and s = 8 p (from BGR), the 4:4:4 forms are the 4:2:2 expressions: (8 p + 2^18) >> 19 = (p + 2^15) >> 16.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "chroma_internal.h"
+
+namespace fldr_chroma_impl {
+
+#define CK_TX 64                 // threads along a row
+#define CK_TY 4                  // rows per block
+
+template <typename T> struct Smp;
+template <> struct Smp<uint8_t> { static constexpr int RUN = RUN8, MID = 128, MAXV = 255; };
+template <> struct Smp<uint16_t> { static constexpr int RUN = RUN16, MID = 512, MAXV = 1023; };
+
+// Values -> dwords through v_perm_b32, never shifts and ORs: hipcc turns "shift, clamp, pack two" into v_ashr_pk_* / v_cvt_pk_u16_* and
+// then trusts upper bits that gfx950 leaves stale (../video/video_kernels.hip, pack4); tests/test_chroma_cpu.py looks at the listing.
+__device__ __forceinline__ uint32_t pack4(int a, int b, int c, int d) {
+    const uint32_t lo = __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x0c0c0400u);     // bytes: a, b, 0, 0
+    const uint32_t hi = __builtin_amdgcn_perm((uint32_t)d, (uint32_t)c, 0x0c0c0400u);     // bytes: c, d, 0, 0
+    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);                                    // a, b, c, d
+}
+__device__ __forceinline__ uint32_t pack2h(int a, int b) { return __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x05040100u); }   // halves: a, b
+
+// NB (8, 16 or 32) bytes at an address aligned to min(NB, 16), as dwords
+template <int NB>
+__device__ __forceinline__ void ld_wide(const uint8_t* p, uint32_t* w) {
+    if (NB == 8) {
+        const uint2 v = *reinterpret_cast<const uint2*>(p);
+        w[0] = v.x; w[1] = v.y;
+    } else {
+#pragma unroll
+        for (int i = 0; i < NB / 16; ++i) {
+            const uint4 v = reinterpret_cast<const uint4*>(p)[i];
+            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
+        }
+    }
+}
+template <int NB>
+__device__ __forceinline__ void st_wide(uint8_t* p, const uint32_t* w) {
+    if (NB == 8) {
+        *reinterpret_cast<uint2*>(p) = make_uint2(w[0], w[1]);
+    } else {
+#pragma unroll
+        for (int i = 0; i < NB / 16; ++i) reinterpret_cast<uint4*>(p)[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
+    }
+}
+
+// N groups of G samples each (G = 1: a plane of single samples; 2: interleaved U, V; 4: a packed 4:2:2 group) from group g0 of `row`:
+// the raw words, s[N * G].  !VEC: group indices clamped to lim - 1.
+template <typename T, int N, int G, bool VEC>
+__device__ __forceinline__ void load_run(const uint8_t* row, int g0, int lim, int* s) {
+    if (VEC) {
+        constexpr int NB = N * G * (int)sizeof(T);
+        uint32_t w[NB / 4];
+        ld_wide<NB>(row + (int64_t)g0 * G * (int)sizeof(T), w);
+#pragma unroll
+        for (int e = 0; e < N * G; ++e)
+            s[e] = sizeof(T) == 1 ? (int)((w[e >> 2] >> (8 * (e & 3))) & 0xffu) : (int)((w[e >> 1] >> (16 * (e & 1))) & 0xffffu);
+    } else {
+        const T* r = reinterpret_cast<const T*>(row);
+#pragma unroll
+        for (int j = 0; j < N; ++j) {
+            const int gi = min(g0 + j, lim - 1);
+#pragma unroll
+            for (int q = 0; q < G; ++q) s[j * G + q] = r[gi * G + q];
+        }
+    }
+}
+
+// The inverse: s[N * G] (values that fit a sample) to groups g0 .. g0 + N - 1; !VEC: only groups below lim are written.
+template <typename T, int N, int G, bool VEC>
+__device__ __forceinline__ void store_run(uint8_t* row, int g0, int lim, const int* s) {
+    if (VEC) {
+        constexpr int NB = N * G * (int)sizeof(T);
+        uint32_t w[NB / 4];
+#pragma unroll
+        for (int i = 0; i < NB / 4; ++i)
+            w[i] = sizeof(T) == 1 ? pack4(s[4 * i], s[4 * i + 1], s[4 * i + 2], s[4 * i + 3]) : pack2h(s[2 * i], s[2 * i + 1]);
+        st_wide<NB>(row + (int64_t)g0 * G * (int)sizeof(T), w);
+    } else {
+        T* r = reinterpret_cast<T*>(row);
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+            if (g0 + j < lim) {
+#pragma unroll
+                for (int q = 0; q < G; ++q) r[(g0 + j) * G + q] = (T)s[j * G + q];
+            }
+    }
+}
+
+// container word <-> code value: bytes are the value; 16-bit words keep it in the high 10 bits (semiplanar: P210 / P410) or the low 10
+template <typename T, int L>
+__device__ __forceinline__ int dec(int w) { return sizeof(T) == 1 ? w : L == FLDR_CHROMA_SEMIPLANAR ? (w >> 6) : (w & 0x3ff); }
+template <typename T, int L>
+__device__ __forceinline__ int enc(int v) { return sizeof(T) == 2 && L == FLDR_CHROMA_SEMIPLANAR ? v << 6 : v; }
+
+// ---- (a) YUV frames -> planar BGR ------------------------------------------------------------------------------------------------
+struct InArgs {
+    const uint8_t* plane[MAX_FRAMES][3];
+    int64_t pitch[MAX_FRAMES][3];    // bytes
+    uint8_t* dst;                    // [n][3][H][W] of T
+    int H, W;
+    YuvCoeffs k;
+};
+
+template <typename T, int S, int L, bool VEC>
+__global__ __launch_bounds__(CK_TX * CK_TY) void chroma_to_planar_kernel(InArgs a) {
+    constexpr int R = Smp<T>::RUN, MID = Smp<T>::MID, MAXV = Smp<T>::MAXV;
+    constexpr bool FULL = S == FLDR_CHROMA_444;
+    constexpr int NC = FULL ? R : R / 2;                             // chroma samples under the run
+    const int x0 = R * (blockIdx.x * CK_TX + threadIdx.x);
+    const int y = blockIdx.y * CK_TY + threadIdx.y;
+    const int f = blockIdx.z;
+    const int H = a.H, W = a.W;
+    if (x0 >= W || y >= H) return;
+    const int cw = FULL ? W : (W + 1) >> 1;
+    const int c0 = FULL ? x0 : x0 >> 1;
+    const int ce = min(c0 + NC, cw - 1);                             // 4:2:2: the chroma sample right of the run (clamped)
+    int yy[R], u[NC + 1], v[NC + 1];
+    const uint8_t* row0 = a.plane[f][0] + (int64_t)y * a.pitch[f][0];
+    if constexpr (L == FLDR_CHROMA_UYVY || L == FLDR_CHROMA_YUYV) {            // 4:2:2, bytes
+        constexpr int YO = L == FLDR_CHROMA_UYVY ? 1 : 0, UO = 1 - YO, VO = UO + 2;
+        int m[NC * 4];
+        load_run<T, NC, 4, VEC>(row0, c0, cw, m);
+#pragma unroll
+        for (int i = 0; i < NC; ++i) { yy[2 * i] = m[4 * i + YO]; yy[2 * i + 1] = m[4 * i + YO + 2]; u[i] = m[4 * i + UO]; v[i] = m[4 * i + VO]; }
+        u[NC] = row0[4 * ce + UO]; v[NC] = row0[4 * ce + VO];
+    } else {
+        load_run<T, R, 1, VEC>(row0, x0, W, yy);
+#pragma unroll
+        for (int j = 0; j < R; ++j) yy[j] = dec<T, L>(yy[j]);
+        const uint8_t* row1 = a.plane[f][1] + (int64_t)y * a.pitch[f][1];
+        if constexpr (L == FLDR_CHROMA_SEMIPLANAR) {
+            int m[NC * 2];
+            load_run<T, NC, 2, VEC>(row1, c0, cw, m);
+#pragma unroll
+            for (int i = 0; i < NC; ++i) { u[i] = dec<T, L>(m[2 * i]); v[i] = dec<T, L>(m[2 * i + 1]); }
+            if (!FULL) { u[NC] = dec<T, L>(reinterpret_cast<const T*>(row1)[2 * ce]); v[NC] = dec<T, L>(reinterpret_cast<const T*>(row1)[2 * ce + 1]); }
+        } else {
+            const uint8_t* row2 = a.plane[f][2] + (int64_t)y * a.pitch[f][2];
+            load_run<T, NC, 1, VEC>(row1, c0, cw, u);
+            load_run<T, NC, 1, VEC>(row2, c0, cw, v);
+#pragma unroll
+            for (int i = 0; i < NC; ++i) { u[i] = dec<T, L>(u[i]); v[i] = dec<T, L>(v[i]); }
+            if (!FULL) { u[NC] = dec<T, L>(reinterpret_cast<const T*>(row1)[ce]); v[NC] = dec<T, L>(reinterpret_cast<const T*>(row2)[ce]); }
+        }
+    }
+    const YuvCoeffs& k = a.k;
+    int bb[R], gg[R], rr[R];
+#pragma unroll
+    for (int j = 0; j < R; ++j) {
+        // h = C[ca] + C[cb]: even x -> both its own column, odd x -> the columns left and right of it (the right one clamped); x0 is even
+        const int ia = FULL ? j : j >> 1, ib = FULL ? j : (j + 1) >> 1;
+        const int cu = 4 * (u[ia] + u[ib]) - 8 * MID;
+        const int cv = 4 * (v[ia] + v[ib]) - 8 * MID;
+        const int yv = (yy[j] - k.yoff) * 8 * k.ky;
+        rr[j] = min(max((yv + k.krv * cv + (1 << 18)) >> 19, 0), MAXV);
+        gg[j] = min(max((yv - k.kgu * cu - k.kgv * cv + (1 << 18)) >> 19, 0), MAXV);
+        bb[j] = min(max((yv + k.kbu * cu + (1 << 18)) >> 19, 0), MAXV);
+    }
+    const int64_t HW = (int64_t)H * W;
+    uint8_t* d = a.dst + ((int64_t)f * 3 * HW + (int64_t)y * W) * (int64_t)sizeof(T);
+    store_run<T, R, 1, VEC>(d, x0, W, bb);
+    store_run<T, R, 1, VEC>(d + HW * (int64_t)sizeof(T), x0, W, gg);
+    store_run<T, R, 1, VEC>(d + 2 * HW * (int64_t)sizeof(T), x0, W, rr);
+}
+
+// ---- (b) planar BGR frame -> YUV frame -----------------------------------------------------------------------------------------
+struct OutArgs {
+    const uint8_t* src;              // [3][H][W] of T
+    uint8_t* plane[3];
+    int64_t pitch[3];                // bytes
+    int H, W;
+    YuvCoeffs k;
+};
+
+template <typename T, int S, int L, bool VEC>
+__global__ __launch_bounds__(CK_TX * CK_TY) void chroma_from_planar_kernel(OutArgs a) {
+    constexpr int R = Smp<T>::RUN, MID = Smp<T>::MID, MAXV = Smp<T>::MAXV;
+    constexpr bool FULL = S == FLDR_CHROMA_444;
+    constexpr int NC = FULL ? R : R / 2;
+    const int x0 = R * (blockIdx.x * CK_TX + threadIdx.x);
+    const int y = blockIdx.y * CK_TY + threadIdx.y;
+    const int H = a.H, W = a.W;
+    if (x0 >= W || y >= H) return;
+    const int cw = FULL ? W : (W + 1) >> 1;
+    const int c0 = FULL ? x0 : x0 >> 1;
+    const int64_t HW = (int64_t)H * W;
+    const YuvCoeffs& k = a.k;
+    // pixels x0 - 1 .. x0 + R - 1 (clamped into the row) of the three planes: px[c][0 .. R]; the left neighbour only feeds 4:2:2 chroma
+    int px[3][R + 1];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const uint8_t* row = a.src + ((int64_t)c * HW + (int64_t)y * W) * (int64_t)sizeof(T);
+        px[c][0] = FULL ? 0 : (int)reinterpret_cast<const T*>(row)[max(x0 - 1, 0)];
+        load_run<T, R, 1, VEC>(row, x0, W, px[c] + 1);
+    }
+    int yb[R], pu[R + 1], pv[R + 1];
+#pragma unroll
+    for (int m = 0; m <= R; ++m) {
+        const int b = px[0][m], g = px[1][m], r = px[2][m];
+        pu[m] = k.kur * r + k.kug * g + k.kub * b;
+        pv[m] = k.kvr * r + k.kvg * g + k.kvb * b;
+        if (m) yb[m - 1] = enc<T, L>(min(max(((k.kyr * r + k.kyg * g + k.kyb * b + (1 << 15)) >> 16) + k.yoff, 0), MAXV));
+    }
+    int uo[NC], vo[NC];
+#pragma unroll
+    for (int i = 0; i < NC; ++i) {
+        // 4:2:2: chroma column c0 + i takes luma x0 + 2 i - 1, x0 + 2 i, x0 + 2 i + 1 weighted 1, 2, 1 (twice: the weights sum to 8)
+        const int su = FULL ? 8 * pu[i + 1] : 2 * (pu[2 * i] + 2 * pu[2 * i + 1] + pu[2 * i + 2]);
+        const int sv = FULL ? 8 * pv[i + 1] : 2 * (pv[2 * i] + 2 * pv[2 * i + 1] + pv[2 * i + 2]);
+        uo[i] = enc<T, L>(min(max(((su + (1 << 18)) >> 19) + MID, 0), MAXV));
+        vo[i] = enc<T, L>(min(max(((sv + (1 << 18)) >> 19) + MID, 0), MAXV));
+    }
+    uint8_t* row0 = a.plane[0] + (int64_t)y * a.pitch[0];
+    if constexpr (L == FLDR_CHROMA_UYVY || L == FLDR_CHROMA_YUYV) {
+        // odd W: the run's last pixel was read clamped, so the second luma byte of the last group is a copy of the last luma sample
+        constexpr int YO = L == FLDR_CHROMA_UYVY ? 1 : 0, UO = 1 - YO, VO = UO + 2;
+        int m[NC * 4];
+#pragma unroll
+        for (int i = 0; i < NC; ++i) { m[4 * i + YO] = yb[2 * i]; m[4 * i + YO + 2] = yb[2 * i + 1]; m[4 * i + UO] = uo[i]; m[4 * i + VO] = vo[i]; }
+        store_run<T, NC, 4, VEC>(row0, c0, cw, m);
+    } else {
+        store_run<T, R, 1, VEC>(row0, x0, W, yb);
+        uint8_t* row1 = a.plane[1] + (int64_t)y * a.pitch[1];
+        if constexpr (L == FLDR_CHROMA_SEMIPLANAR) {
+            int m[NC * 2];
+#pragma unroll
+            for (int i = 0; i < NC; ++i) { m[2 * i] = uo[i]; m[2 * i + 1] = vo[i]; }
+            store_run<T, NC, 2, VEC>(row1, c0, cw, m);
+        } else {
+            store_run<T, NC, 1, VEC>(row1, c0, cw, uo);
+            store_run<T, NC, 1, VEC>(a.plane[2] + (int64_t)y * a.pitch[2], c0, cw, vo);
+        }
+    }
+}
+
+// ---- launchers -----------------------------------------------------------------------------------------------------------------
+static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static int planes_used(int layout) { return layout == FLDR_CHROMA_PLANAR ? 3 : layout == FLDR_CHROMA_SEMIPLANAR ? 2 : 1; }
+
+// Call GO(S, L) for the (sampling, layout) of `fmt`; the packed layouts exist for bytes at 4:2:2 only (the caller checked the format).
+#define CK_DISPATCH(T, fmt)                                                                      \
+    do {                                                                                         \
+        if ((fmt).sampling == FLDR_CHROMA_444) {                                                 \
+            if ((fmt).layout == FLDR_CHROMA_PLANAR) GO(FLDR_CHROMA_444, FLDR_CHROMA_PLANAR);     \
+            else GO(FLDR_CHROMA_444, FLDR_CHROMA_SEMIPLANAR);                                    \
+        } else if ((fmt).layout == FLDR_CHROMA_PLANAR) GO(FLDR_CHROMA_422, FLDR_CHROMA_PLANAR);  \
+        else if ((fmt).layout == FLDR_CHROMA_SEMIPLANAR) GO(FLDR_CHROMA_422, FLDR_CHROMA_SEMIPLANAR); \
+        else if constexpr (sizeof(T) == 1) {                                                     \
+            if ((fmt).layout == FLDR_CHROMA_UYVY) GO(FLDR_CHROMA_422, FLDR_CHROMA_UYVY);         \
+            else GO(FLDR_CHROMA_422, FLDR_CHROMA_YUYV);                                          \
+        }                                                                                        \
+    } while (0)
+
+template <typename T>
+static int to_planar_t(const fldr_chroma_frame* in, int n, const fldr_chroma_format& fmt, const YuvCoeffs& k, void* planar, int H, int W,
+                       hipStream_t stream) {
+    constexpr int R = Smp<T>::RUN;
+    InArgs a;
+    const int np = planes_used(fmt.layout);
+    bool vec = W % R == 0 && al16(planar);
+    for (int f = 0; f < MAX_FRAMES; ++f)
+        for (int p = 0; p < 3; ++p) {
+            const bool used = f < n && p < np;
+            a.plane[f][p] = used ? (const uint8_t*)in[f].plane[p] : nullptr;
+            a.pitch[f][p] = used ? in[f].pitch[p] : 0;
+            if (used) vec = vec && al16(in[f].plane[p]) && (in[f].pitch[p] & 15) == 0;
+        }
+    a.dst = (uint8_t*)planar; a.H = H; a.W = W; a.k = k;
+    const dim3 grid(((W + R - 1) / R + CK_TX - 1) / CK_TX, (H + CK_TY - 1) / CK_TY, n), block(CK_TX, CK_TY);
+#define GO(S, L)                                                                                          \
+    do {                                                                                                  \
+        if (vec) hipLaunchKernelGGL((chroma_to_planar_kernel<T, S, L, true>), grid, block, 0, stream, a); \
+        else hipLaunchKernelGGL((chroma_to_planar_kernel<T, S, L, false>), grid, block, 0, stream, a);    \
+    } while (0)
+    CK_DISPATCH(T, fmt);
+#undef GO
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+template <typename T>
+static int from_planar_t(const void* planar, const fldr_chroma_frame& out, const fldr_chroma_format& fmt, const YuvCoeffs& k, int H, int W,
+                         hipStream_t stream) {
+    constexpr int R = Smp<T>::RUN;
+    OutArgs a;
+    const int np = planes_used(fmt.layout);
+    bool vec = W % R == 0 && al16(planar);
+    for (int p = 0; p < 3; ++p) {
+        a.plane[p] = p < np ? (uint8_t*)out.plane[p] : nullptr;
+        a.pitch[p] = p < np ? out.pitch[p] : 0;
+        if (p < np) vec = vec && al16(out.plane[p]) && (out.pitch[p] & 15) == 0;
+    }
+    a.src = (const uint8_t*)planar; a.H = H; a.W = W; a.k = k;
+    const dim3 grid(((W + R - 1) / R + CK_TX - 1) / CK_TX, (H + CK_TY - 1) / CK_TY, 1), block(CK_TX, CK_TY);
+#define GO(S, L)                                                                                            \
+    do {                                                                                                    \
+        if (vec) hipLaunchKernelGGL((chroma_from_planar_kernel<T, S, L, true>), grid, block, 0, stream, a); \
+        else hipLaunchKernelGGL((chroma_from_planar_kernel<T, S, L, false>), grid, block, 0, stream, a);    \
+    } while (0)
+    CK_DISPATCH(T, fmt);
+#undef GO
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
+
+int to_planar(const fldr_chroma_frame* in, int n, const fldr_chroma_format& fmt, const YuvCoeffs& k, void* planar, int H, int W, hipStream_t stream) {
+    return fmt.depth == 10 ? to_planar_t<uint16_t>(in, n, fmt, k, planar, H, W, stream) : to_planar_t<uint8_t>(in, n, fmt, k, planar, H, W, stream);
+}
+
+int from_planar(const void* planar, const fldr_chroma_frame& out, const fldr_chroma_format& fmt, const YuvCoeffs& k, int H, int W, hipStream_t stream) {
+    return fmt.depth == 10 ? from_planar_t<uint16_t>(planar, out, fmt, k, H, W, stream) : from_planar_t<uint8_t>(planar, out, fmt, k, H, W, stream);
+}
+
+}  // namespace fldr_chroma_impl

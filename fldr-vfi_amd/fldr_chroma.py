@@ -1,0 +1,274 @@
+"""ctypes binding of libfldr_chroma.so (include/fldr_chroma.h) — frame interpolation on YUV 4:2:2 and 4:4:4 frames at 8 and 10 bits.
+
+    nc = NativeChroma(fldr_model.NativeModel.from_npz(fldr_harness.DEFAULT_WEIGHTS))
+    outs = nc.forward((f0, f1), t=[0.5], in_format=Format("422", "semiplanar", depth=10))      # P210 -> list of n_t output frames
+    bgr = nc.to_planar([f0, f1], fmt)                 # the input converter alone: planar BGR [2,3,H,W]
+    frame = nc.from_planar(bgr[0], fmt)               # the output converter alone
+    s = Session(native_model, H, W, n_t=3, in_format=Format("422", "uyvy"))    # host frames (numpy planes), each uploaded once
+
+A device frame is a tuple of 2-D device tensors, one per plane (planar: Y, U, V; semiplanar: Y, UV; uyvy / yuyv: one plane), uint8, or
+uint16 at depth 10, each [rows, samples per row] with stride(1) == 1; the pitch is stride(0), so views into wider buffers work.  Host
+frames of a Session are the same as numpy arrays.  Every call enqueues on torch's current stream of the model's device and returns
+without synchronising.  No fallback: a missing library raises at load.
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+import fldr_model
+from fldr_video import HostStream, _stream_ptr, frame_struct as _video_frame_struct
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+LIB_PATH = os.path.join(_HERE, "libfldr_chroma.so")
+CHROMA_VERSION = 100              # include/fldr_chroma.h: FLDR_CHROMA_VERSION
+
+SAMPLINGS = {"422": 0, "444": 1}
+LAYOUTS = {"planar": 0, "semiplanar": 1, "uyvy": 2, "yuyv": 3}
+MATRICES = {"bt601": 0, "bt709": 1}
+RANGES = {"limited": 0, "full": 1}
+E_ARG, E_FORMAT, E_PITCH, E_PLANE, E_WORKSPACE, E_DEVICE = -700, -701, -702, -703, -704, -705
+RUN = {8: 16, 10: 8}              # chroma_internal.h: luma pixels per thread at each depth (the wide form needs W % RUN == 0)
+
+
+class Format(ctypes.Structure):
+    _fields_ = [("sampling", ctypes.c_int32), ("layout", ctypes.c_int32), ("matrix", ctypes.c_int32), ("range", ctypes.c_int32),
+                ("depth", ctypes.c_int32), ("reserved", ctypes.c_int32 * 3)]
+
+    def __init__(self, sampling="422", layout="planar", matrix="bt709", range="limited", depth=8):
+        pick = lambda table, v: table[v] if isinstance(v, str) else int(v)
+        super().__init__(pick(SAMPLINGS, sampling), pick(LAYOUTS, layout), pick(MATRICES, matrix), pick(RANGES, range), int(depth))
+
+    def copy(self):
+        return Format(self.sampling, self.layout, self.matrix, self.range, self.depth)
+
+    @property
+    def bits(self):
+        """8 or 10: the depth with the 0 alias resolved."""
+        return 10 if self.depth == 10 else 8
+
+
+class Frame(ctypes.Structure):
+    _fields_ = [("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
+
+
+class IO(ctypes.Structure):
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("in_", Frame * 2), ("out_format", Format),
+                ("n_t", ctypes.c_int32), ("t", ctypes.c_void_p), ("out", ctypes.POINTER(Frame))]
+
+
+class SessionConfig(ctypes.Structure):
+    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("out_format", Format), ("n_t", ctypes.c_int32),
+                ("device", ctypes.c_int32), ("t", ctypes.POINTER(ctypes.c_float)), ("reserved", ctypes.c_int32 * 4)]
+
+
+_SIGNATURES = {
+    "fldr_chroma_version": (ctypes.c_int, []),
+    "fldr_chroma_error_string": (ctypes.c_char_p, [ctypes.c_int]),
+    "fldr_chroma_sizeof": (ctypes.c_int, [ctypes.c_int]),
+    "fldr_chroma_to_planar": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.c_int, ctypes.POINTER(Format), ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                             ctypes.c_void_p]),
+    "fldr_chroma_from_planar": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Format), ctypes.POINTER(Frame), ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_void_p]),
+    "fldr_chroma_workspace_bytes": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "fldr_chroma_forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IO), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+    "fldr_chroma_session_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SessionConfig), ctypes.POINTER(ctypes.c_void_p)]),
+    "fldr_chroma_session_push": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.POINTER(Frame), ctypes.POINTER(ctypes.c_int)]),
+    "fldr_chroma_session_reset": (ctypes.c_int, [ctypes.c_void_p]),
+    "fldr_chroma_session_destroy": (None, [ctypes.c_void_p]),
+}
+EXPORTS = tuple(_SIGNATURES)
+_lib = None
+
+
+class ChromaError(RuntimeError):
+    def __init__(self, what, code):
+        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_chroma_error_string(code).decode(), code))
+        self.code = code
+
+
+def lib():
+    """The loaded libfldr_chroma.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
+    global _lib
+    if _lib is None:
+        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (Format, Frame, IO, SessionConfig), "fldr_chroma", CHROMA_VERSION)
+    return _lib
+
+
+def _check(code, what):
+    if code != 0:
+        raise ChromaError(what, code)
+
+
+# ---- geometry ---------------------------------------------------------------------------------------------------------------------
+def plane_shapes(fmt, H, W):
+    """[(rows, samples per row)] of each plane of an H x W frame: bytes at depth 8, 16-bit words at depth 10 (plane_dtype)."""
+    half = (W + 1) // 2
+    if fmt.layout >= 2:
+        return [(H, 4 * half)]
+    cw = W if fmt.sampling == 1 else half
+    return [(H, W), (H, 2 * cw)] if fmt.layout == 1 else [(H, W), (H, cw), (H, cw)]
+
+
+def plane_dtype(fmt, numpy=False):
+    """The element type of a frame's planes: uint8, or uint16 for a Format of depth 10."""
+    if fmt.bits == 10:
+        return np.uint16 if numpy else torch.uint16
+    return np.uint8 if numpy else torch.uint8
+
+
+def frame_struct(planes):
+    """A Frame from a tuple of 2-D plane arrays (torch tensors or numpy arrays) with unit column stride."""
+    v = _video_frame_struct(planes)
+    f = Frame()
+    for p in range(3):
+        f.plane[p], f.pitch[p] = v.plane[p], v.pitch[p]
+    return f
+
+
+def empty_frame(fmt, H, W, device):
+    return tuple(torch.empty(r, c, dtype=plane_dtype(fmt), device=device) for r, c in plane_shapes(fmt, H, W))
+
+
+def luma_size(frame, fmt):
+    """(H, W) of a frame from its first plane; a packed plane tells W only up to its parity, so pass W where it is odd."""
+    r, c = frame[0].shape
+    return (r, c // 2) if fmt.layout >= 2 else (r, c)
+
+
+# ---- the converters alone (they need no model) ---------------------------------------------------------------------------------------
+def to_planar(frames, fmt, planar=None, W=None, stream=None):
+    """fldr_chroma_to_planar: a list of frames in `fmt` (tuples of device plane tensors, pitches from their strides) -> planar BGR
+    [n,3,H,W] (uint8; uint16 at depth 10; `planar` when given).  W: the luma width of a packed frame when it is odd."""
+    H, w = luma_size(frames[0], fmt)
+    W = w if W is None else W
+    device = frames[0][0].device
+    if planar is None:
+        planar = torch.empty(len(frames), 3, H, W, dtype=plane_dtype(fmt), device=device)
+    arr = (Frame * len(frames))(*[frame_struct(f) for f in frames])
+    _check(lib().fldr_chroma_to_planar(arr, len(frames), ctypes.byref(fmt), ctypes.c_void_p(planar.data_ptr()), int(H), int(W),
+                                       _stream_ptr(device, stream)), "fldr_chroma_to_planar")
+    return planar
+
+
+def from_planar(planar, fmt, out=None, stream=None):
+    """fldr_chroma_from_planar: a planar BGR device tensor [3,H,W] with contiguous rows and planes (uint8; uint16 at depth 10) -> one
+    frame in `fmt` (`out`: a tuple of plane tensors, pitches from their strides; allocated packed otherwise)."""
+    _, H, W = planar.shape
+    assert planar.is_contiguous() and planar.dtype == plane_dtype(fmt)
+    if out is None:
+        out = empty_frame(fmt, H, W, planar.device)
+    fr = frame_struct(out)
+    _check(lib().fldr_chroma_from_planar(ctypes.c_void_p(planar.data_ptr()), ctypes.byref(fmt), ctypes.byref(fr), int(H), int(W),
+                                         _stream_ptr(planar.device, stream)), "fldr_chroma_from_planar")
+    return out
+
+
+class NativeChroma:
+    """4:2:2 / 4:4:4 forwards and the two converters on a fldr_model.NativeModel (read-only: forwards on several streams, each with its
+    own workspace, may run at once)."""
+
+    def __init__(self, native_model):
+        lib()
+        self.model = native_model
+        self.device = native_model.device
+
+    def workspace_bytes(self, H, W, n_t=1):
+        n = lib().fldr_chroma_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
+        if n < 0:
+            raise ChromaError("fldr_chroma_workspace_bytes", int(n))
+        return int(n)
+
+    def workspace(self, H, W, n_t=1):
+        return torch.empty(self.workspace_bytes(H, W, n_t), dtype=torch.uint8, device=self.device)
+
+    def planar(self, ws, H, W, n_t=1, in_depth=8, out_depth=8):
+        """Views into a workspace after a forward: (pair [2,3,H,W], outputs [n_t][3,H,W]) — the planar BGR frames of the model, uint8, or
+        uint16 for the side whose format had depth 10."""
+        mb = fldr_model.lib().fldr_model_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
+        al = lambda v: (v + 255) // 256 * 256
+        bi, bo = (2 if in_depth == 10 else 1), (2 if out_depth == 10 else 1)
+        as_ = lambda x, b, shape: (x.view(torch.uint16) if b == 2 else x).view(shape)
+        pair = as_(ws[al(mb):al(mb) + 6 * H * W * bi], bi, (2, 3, H, W))
+        o = al(mb) + al(6 * H * W * bi)
+        st = al(3 * H * W * bo)
+        outs = [as_(ws[o + k * st:o + k * st + 3 * H * W * bo], bo, (3, H, W)) for k in range(n_t)]
+        return pair, outs
+
+    to_planar = staticmethod(to_planar)
+    from_planar = staticmethod(from_planar)
+
+    def forward_io(self, io, ws, stream=None):
+        """The raw call; returns the code without raising (tests of the error contract)."""
+        return lib().fldr_chroma_forward(self.model._h, ctypes.byref(io), ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                         ws.numel() if ws is not None else 0, _stream_ptr(self.device, stream))
+
+    def _t(self, t):
+        """t as the float32 device tensor a forward reads: one that already is (contiguous, on a device) is used in place."""
+        if torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous():
+            return t
+        return torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device)
+
+    def make_io(self, frames, t, in_format, out_format, outs, H, W):
+        io = IO()
+        io.H, io.W = int(H), int(W)
+        io.in_format, io.out_format = in_format, out_format
+        for i, fr in enumerate(frames):
+            io.in_[i] = frame_struct(fr)
+        arr = (Frame * len(outs))(*[frame_struct(o) for o in outs])
+        io.n_t, io.t, io.out = len(outs), t.data_ptr(), ctypes.cast(arr, ctypes.POINTER(Frame))
+        io._keep = arr
+        return io
+
+    def forward(self, frames, t=0.5, in_format=None, out_format=None, outs=None, ws=None, W=None, stream=None):
+        """frames: (I0, I1), each a tuple of plane tensors in in_format; t: n_t values (a float32 device tensor is used in place: a
+        captured call reads it at replay).  -> the n_t output frames (`outs` when given; allocated packed otherwise)."""
+        in_format = in_format or Format()
+        out_format = out_format or in_format.copy()
+        H, w = luma_size(frames[0], in_format)
+        W = w if W is None else W
+        tt = self._t(t)
+        n_t = tt.numel()
+        if outs is None:
+            outs = [empty_frame(out_format, H, W, self.device) for _ in range(n_t)]
+        if ws is None:
+            ws = self.workspace(H, W, n_t)
+        io = self.make_io(frames, tt, in_format, out_format, outs, H, W)
+        _check(self.forward_io(io, ws, stream), "fldr_chroma_forward")
+        return outs
+
+
+class Session(HostStream):
+    """fldr_chroma_session: host frames (tuples of numpy planes) pushed one by one; each push after the first returns n_t frames."""
+
+    _destroy = staticmethod(lambda h: lib().fldr_chroma_session_destroy(h))
+
+    def __init__(self, native_model, H, W, n_t=1, in_format=None, out_format=None, t=None):
+        in_format = in_format or Format()
+        out_format = out_format or in_format.copy()
+        cfg = SessionConfig()
+        cfg.H, cfg.W, cfg.n_t, cfg.device = int(H), int(W), int(n_t), native_model.device.index or 0
+        cfg.in_format, cfg.out_format = in_format, out_format
+        if t is not None:
+            ta = (ctypes.c_float * n_t)(*[float(v) for v in t])
+            cfg.t = ctypes.cast(ta, ctypes.POINTER(ctypes.c_float))
+        self._h = ctypes.c_void_p()
+        self.model = native_model                                    # the session uses the model: keep it alive
+        _check(lib().fldr_chroma_session_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_chroma_session_create")
+        self.H, self.W, self.n_t, self.in_format, self.out_format = int(H), int(W), int(n_t), in_format, out_format
+        self._outs = [tuple(np.empty(s, plane_dtype(out_format, numpy=True)) for s in plane_shapes(out_format, H, W)) for _ in range(n_t)]
+
+    def _out_structs(self):
+        return (Frame * len(self._outs))(*[frame_struct(o) for o in self._outs])
+
+    def push(self, frame):
+        """-> [] or a list of n_t output frames (tuples of numpy planes, fresh copies)."""
+        fr = frame_struct(frame)
+        n = ctypes.c_int(-1)
+        _check(lib().fldr_chroma_session_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n)), "fldr_chroma_session_push")
+        self.last_n_out = n.value
+        return self._taken(n.value)
+
+    def reset(self):
+        _check(lib().fldr_chroma_session_reset(self._h), "fldr_chroma_session_reset")
