@@ -10,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../video/yuv_run_device.h"
 #include "chroma_internal.h"
 
 namespace fldr_chroma_impl {
@@ -17,91 +18,9 @@ namespace fldr_chroma_impl {
 #define CK_TX 64                 // threads along a row
 #define CK_TY 4                  // rows per block
 
-template <typename T> struct Smp;
-template <> struct Smp<uint8_t> { static constexpr int RUN = RUN8, MID = 128, MAXV = 255; };
-template <> struct Smp<uint16_t> { static constexpr int RUN = RUN16, MID = 512, MAXV = 1023; };
+using namespace fldr_yuv_run;                      // Smp, load_run / store_run, dec / enc
 
-// Values -> dwords through v_perm_b32, never shifts and ORs: hipcc turns "shift, clamp, pack two" into v_ashr_pk_* / v_cvt_pk_u16_* and
-// then trusts upper bits that gfx950 leaves stale (../video/video_kernels.hip, pack4); tests/test_chroma_cpu.py looks at the listing.
-__device__ __forceinline__ uint32_t pack4(int a, int b, int c, int d) {
-    const uint32_t lo = __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x0c0c0400u);     // bytes: a, b, 0, 0
-    const uint32_t hi = __builtin_amdgcn_perm((uint32_t)d, (uint32_t)c, 0x0c0c0400u);     // bytes: c, d, 0, 0
-    return __builtin_amdgcn_perm(hi, lo, 0x05040100u);                                    // a, b, c, d
-}
-__device__ __forceinline__ uint32_t pack2h(int a, int b) { return __builtin_amdgcn_perm((uint32_t)b, (uint32_t)a, 0x05040100u); }   // halves: a, b
-
-// NB (8, 16 or 32) bytes at an address aligned to min(NB, 16), as dwords
-template <int NB>
-__device__ __forceinline__ void ld_wide(const uint8_t* p, uint32_t* w) {
-    if (NB == 8) {
-        const uint2 v = *reinterpret_cast<const uint2*>(p);
-        w[0] = v.x; w[1] = v.y;
-    } else {
-#pragma unroll
-        for (int i = 0; i < NB / 16; ++i) {
-            const uint4 v = reinterpret_cast<const uint4*>(p)[i];
-            w[4 * i] = v.x; w[4 * i + 1] = v.y; w[4 * i + 2] = v.z; w[4 * i + 3] = v.w;
-        }
-    }
-}
-template <int NB>
-__device__ __forceinline__ void st_wide(uint8_t* p, const uint32_t* w) {
-    if (NB == 8) {
-        *reinterpret_cast<uint2*>(p) = make_uint2(w[0], w[1]);
-    } else {
-#pragma unroll
-        for (int i = 0; i < NB / 16; ++i) reinterpret_cast<uint4*>(p)[i] = make_uint4(w[4 * i], w[4 * i + 1], w[4 * i + 2], w[4 * i + 3]);
-    }
-}
-
-// N groups of G samples each (G = 1: a plane of single samples; 2: interleaved U, V; 4: a packed 4:2:2 group) from group g0 of `row`:
-// the raw words, s[N * G].  !VEC: group indices clamped to lim - 1.
-template <typename T, int N, int G, bool VEC>
-__device__ __forceinline__ void load_run(const uint8_t* row, int g0, int lim, int* s) {
-    if (VEC) {
-        constexpr int NB = N * G * (int)sizeof(T);
-        uint32_t w[NB / 4];
-        ld_wide<NB>(row + (int64_t)g0 * G * (int)sizeof(T), w);
-#pragma unroll
-        for (int e = 0; e < N * G; ++e)
-            s[e] = sizeof(T) == 1 ? (int)((w[e >> 2] >> (8 * (e & 3))) & 0xffu) : (int)((w[e >> 1] >> (16 * (e & 1))) & 0xffffu);
-    } else {
-        const T* r = reinterpret_cast<const T*>(row);
-#pragma unroll
-        for (int j = 0; j < N; ++j) {
-            const int gi = min(g0 + j, lim - 1);
-#pragma unroll
-            for (int q = 0; q < G; ++q) s[j * G + q] = r[gi * G + q];
-        }
-    }
-}
-
-// The inverse: s[N * G] (values that fit a sample) to groups g0 .. g0 + N - 1; !VEC: only groups below lim are written.
-template <typename T, int N, int G, bool VEC>
-__device__ __forceinline__ void store_run(uint8_t* row, int g0, int lim, const int* s) {
-    if (VEC) {
-        constexpr int NB = N * G * (int)sizeof(T);
-        uint32_t w[NB / 4];
-#pragma unroll
-        for (int i = 0; i < NB / 4; ++i)
-            w[i] = sizeof(T) == 1 ? pack4(s[4 * i], s[4 * i + 1], s[4 * i + 2], s[4 * i + 3]) : pack2h(s[2 * i], s[2 * i + 1]);
-        st_wide<NB>(row + (int64_t)g0 * G * (int)sizeof(T), w);
-    } else {
-        T* r = reinterpret_cast<T*>(row);
-#pragma unroll
-        for (int j = 0; j < N; ++j)
-            if (g0 + j < lim) {
-#pragma unroll
-                for (int q = 0; q < G; ++q) r[(g0 + j) * G + q] = (T)s[j * G + q];
-            }
-    }
-}
-
-// container word <-> code value: bytes are the value; 16-bit words keep it in the high 10 bits (semiplanar: P210 / P410) or the low 10
-template <typename T, int L>
-__device__ __forceinline__ int dec(int w) { return sizeof(T) == 1 ? w : L == FLDR_CHROMA_SEMIPLANAR ? (w >> 6) : (w & 0x3ff); }
-template <typename T, int L>
-__device__ __forceinline__ int enc(int v) { return sizeof(T) == 2 && L == FLDR_CHROMA_SEMIPLANAR ? v << 6 : v; }
+template <typename T> constexpr int RUN = sizeof(T) == 1 ? RUN8 : RUN16;
 
 // ---- (a) YUV frames -> planar BGR ------------------------------------------------------------------------------------------------
 struct InArgs {
@@ -114,8 +33,8 @@ struct InArgs {
 
 template <typename T, int S, int L, bool VEC>
 __global__ __launch_bounds__(CK_TX * CK_TY) void chroma_to_planar_kernel(InArgs a) {
-    constexpr int R = Smp<T>::RUN, MID = Smp<T>::MID, MAXV = Smp<T>::MAXV;
-    constexpr bool FULL = S == FLDR_CHROMA_444;
+    constexpr int R = RUN<T>, MID = Smp<T>::MID, MAXV = Smp<T>::MAXV;
+    constexpr bool FULL = S == FLDR_CHROMA_444, HI = L == FLDR_CHROMA_SEMIPLANAR;   // HI: 16-bit words keep the value high
     constexpr int NC = FULL ? R : R / 2;                             // chroma samples under the run
     const int x0 = R * (blockIdx.x * CK_TX + threadIdx.x);
     const int y = blockIdx.y * CK_TY + threadIdx.y;
@@ -137,21 +56,21 @@ __global__ __launch_bounds__(CK_TX * CK_TY) void chroma_to_planar_kernel(InArgs 
     } else {
         load_run<T, R, 1, VEC>(row0, x0, W, yy);
 #pragma unroll
-        for (int j = 0; j < R; ++j) yy[j] = dec<T, L>(yy[j]);
+        for (int j = 0; j < R; ++j) yy[j] = dec<T, HI>(yy[j]);
         const uint8_t* row1 = a.plane[f][1] + (int64_t)y * a.pitch[f][1];
         if constexpr (L == FLDR_CHROMA_SEMIPLANAR) {
             int m[NC * 2];
             load_run<T, NC, 2, VEC>(row1, c0, cw, m);
 #pragma unroll
-            for (int i = 0; i < NC; ++i) { u[i] = dec<T, L>(m[2 * i]); v[i] = dec<T, L>(m[2 * i + 1]); }
-            if (!FULL) { u[NC] = dec<T, L>(reinterpret_cast<const T*>(row1)[2 * ce]); v[NC] = dec<T, L>(reinterpret_cast<const T*>(row1)[2 * ce + 1]); }
+            for (int i = 0; i < NC; ++i) { u[i] = dec<T, HI>(m[2 * i]); v[i] = dec<T, HI>(m[2 * i + 1]); }
+            if (!FULL) { u[NC] = dec<T, HI>(reinterpret_cast<const T*>(row1)[2 * ce]); v[NC] = dec<T, HI>(reinterpret_cast<const T*>(row1)[2 * ce + 1]); }
         } else {
             const uint8_t* row2 = a.plane[f][2] + (int64_t)y * a.pitch[f][2];
             load_run<T, NC, 1, VEC>(row1, c0, cw, u);
             load_run<T, NC, 1, VEC>(row2, c0, cw, v);
 #pragma unroll
-            for (int i = 0; i < NC; ++i) { u[i] = dec<T, L>(u[i]); v[i] = dec<T, L>(v[i]); }
-            if (!FULL) { u[NC] = dec<T, L>(reinterpret_cast<const T*>(row1)[ce]); v[NC] = dec<T, L>(reinterpret_cast<const T*>(row2)[ce]); }
+            for (int i = 0; i < NC; ++i) { u[i] = dec<T, HI>(u[i]); v[i] = dec<T, HI>(v[i]); }
+            if (!FULL) { u[NC] = dec<T, HI>(reinterpret_cast<const T*>(row1)[ce]); v[NC] = dec<T, HI>(reinterpret_cast<const T*>(row2)[ce]); }
         }
     }
     const YuvCoeffs& k = a.k;
@@ -185,8 +104,8 @@ struct OutArgs {
 
 template <typename T, int S, int L, bool VEC>
 __global__ __launch_bounds__(CK_TX * CK_TY) void chroma_from_planar_kernel(OutArgs a) {
-    constexpr int R = Smp<T>::RUN, MID = Smp<T>::MID, MAXV = Smp<T>::MAXV;
-    constexpr bool FULL = S == FLDR_CHROMA_444;
+    constexpr int R = RUN<T>, MID = Smp<T>::MID, MAXV = Smp<T>::MAXV;
+    constexpr bool FULL = S == FLDR_CHROMA_444, HI = L == FLDR_CHROMA_SEMIPLANAR;   // HI: 16-bit words keep the value high
     constexpr int NC = FULL ? R : R / 2;
     const int x0 = R * (blockIdx.x * CK_TX + threadIdx.x);
     const int y = blockIdx.y * CK_TY + threadIdx.y;
@@ -210,7 +129,7 @@ __global__ __launch_bounds__(CK_TX * CK_TY) void chroma_from_planar_kernel(OutAr
         const int b = px[0][m], g = px[1][m], r = px[2][m];
         pu[m] = k.kur * r + k.kug * g + k.kub * b;
         pv[m] = k.kvr * r + k.kvg * g + k.kvb * b;
-        if (m) yb[m - 1] = enc<T, L>(min(max(((k.kyr * r + k.kyg * g + k.kyb * b + (1 << 15)) >> 16) + k.yoff, 0), MAXV));
+        if (m) yb[m - 1] = enc<T, HI>(min(max(((k.kyr * r + k.kyg * g + k.kyb * b + (1 << 15)) >> 16) + k.yoff, 0), MAXV));
     }
     int uo[NC], vo[NC];
 #pragma unroll
@@ -218,8 +137,8 @@ __global__ __launch_bounds__(CK_TX * CK_TY) void chroma_from_planar_kernel(OutAr
         // 4:2:2: chroma column c0 + i takes luma x0 + 2 i - 1, x0 + 2 i, x0 + 2 i + 1 weighted 1, 2, 1 (twice: the weights sum to 8)
         const int su = FULL ? 8 * pu[i + 1] : 2 * (pu[2 * i] + 2 * pu[2 * i + 1] + pu[2 * i + 2]);
         const int sv = FULL ? 8 * pv[i + 1] : 2 * (pv[2 * i] + 2 * pv[2 * i + 1] + pv[2 * i + 2]);
-        uo[i] = enc<T, L>(min(max(((su + (1 << 18)) >> 19) + MID, 0), MAXV));
-        vo[i] = enc<T, L>(min(max(((sv + (1 << 18)) >> 19) + MID, 0), MAXV));
+        uo[i] = enc<T, HI>(min(max(((su + (1 << 18)) >> 19) + MID, 0), MAXV));
+        vo[i] = enc<T, HI>(min(max(((sv + (1 << 18)) >> 19) + MID, 0), MAXV));
     }
     uint8_t* row0 = a.plane[0] + (int64_t)y * a.pitch[0];
     if constexpr (L == FLDR_CHROMA_UYVY || L == FLDR_CHROMA_YUYV) {
@@ -265,7 +184,7 @@ static int planes_used(int layout) { return layout == FLDR_CHROMA_PLANAR ? 3 : l
 template <typename T>
 static int to_planar_t(const fldr_chroma_frame* in, int n, const fldr_chroma_format& fmt, const YuvCoeffs& k, void* planar, int H, int W,
                        hipStream_t stream) {
-    constexpr int R = Smp<T>::RUN;
+    constexpr int R = RUN<T>;
     InArgs a;
     const int np = planes_used(fmt.layout);
     bool vec = W % R == 0 && al16(planar);
@@ -292,7 +211,7 @@ static int to_planar_t(const fldr_chroma_frame* in, int n, const fldr_chroma_for
 template <typename T>
 static int from_planar_t(const void* planar, const fldr_chroma_frame& out, const fldr_chroma_format& fmt, const YuvCoeffs& k, int H, int W,
                          hipStream_t stream) {
-    constexpr int R = Smp<T>::RUN;
+    constexpr int R = RUN<T>;
     OutArgs a;
     const int np = planes_used(fmt.layout);
     bool vec = W % R == 0 && al16(planar);

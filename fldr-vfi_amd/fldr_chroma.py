@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 import fldr_model
-from fldr_video import HostStream, _stream_ptr, frame_struct as _video_frame_struct
+from fldr_video import YuvApi, YuvNative, YuvSession, _stream_ptr, frame_struct as _video_frame_struct, yuv_signatures
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfldr_chroma.so")
@@ -64,19 +64,11 @@ class SessionConfig(ctypes.Structure):
 
 
 _SIGNATURES = {
-    "fldr_chroma_version": (ctypes.c_int, []),
-    "fldr_chroma_error_string": (ctypes.c_char_p, [ctypes.c_int]),
-    "fldr_chroma_sizeof": (ctypes.c_int, [ctypes.c_int]),
+    **yuv_signatures("fldr_chroma_", Frame, IO, SessionConfig),
     "fldr_chroma_to_planar": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.c_int, ctypes.POINTER(Format), ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_void_p]),
     "fldr_chroma_from_planar": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Format), ctypes.POINTER(Frame), ctypes.c_int, ctypes.c_int,
                                                ctypes.c_void_p]),
-    "fldr_chroma_workspace_bytes": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "fldr_chroma_forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IO), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    "fldr_chroma_session_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SessionConfig), ctypes.POINTER(ctypes.c_void_p)]),
-    "fldr_chroma_session_push": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.POINTER(Frame), ctypes.POINTER(ctypes.c_int)]),
-    "fldr_chroma_session_reset": (ctypes.c_int, [ctypes.c_void_p]),
-    "fldr_chroma_session_destroy": (None, [ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
 _lib = None
@@ -127,8 +119,8 @@ def frame_struct(planes):
     return f
 
 
-def empty_frame(fmt, H, W, device):
-    return tuple(torch.empty(r, c, dtype=plane_dtype(fmt), device=device) for r, c in plane_shapes(fmt, H, W))
+_YUV = YuvApi(lib, "fldr_chroma_", ChromaError, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype)
+empty_frame = _YUV.empty_frame
 
 
 def luma_size(frame, fmt):
@@ -165,110 +157,23 @@ def from_planar(planar, fmt, out=None, stream=None):
     return out
 
 
-class NativeChroma:
+class NativeChroma(YuvNative):
     """4:2:2 / 4:4:4 forwards and the two converters on a fldr_model.NativeModel (read-only: forwards on several streams, each with its
     own workspace, may run at once)."""
 
-    def __init__(self, native_model):
-        lib()
-        self.model = native_model
-        self.device = native_model.device
-
-    def workspace_bytes(self, H, W, n_t=1):
-        n = lib().fldr_chroma_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
-        if n < 0:
-            raise ChromaError("fldr_chroma_workspace_bytes", int(n))
-        return int(n)
-
-    def workspace(self, H, W, n_t=1):
-        return torch.empty(self.workspace_bytes(H, W, n_t), dtype=torch.uint8, device=self.device)
-
-    def planar(self, ws, H, W, n_t=1, in_depth=8, out_depth=8):
-        """Views into a workspace after a forward: (pair [2,3,H,W], outputs [n_t][3,H,W]) — the planar BGR frames of the model, uint8, or
-        uint16 for the side whose format had depth 10."""
-        mb = fldr_model.lib().fldr_model_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
-        al = lambda v: (v + 255) // 256 * 256
-        bi, bo = (2 if in_depth == 10 else 1), (2 if out_depth == 10 else 1)
-        as_ = lambda x, b, shape: (x.view(torch.uint16) if b == 2 else x).view(shape)
-        pair = as_(ws[al(mb):al(mb) + 6 * H * W * bi], bi, (2, 3, H, W))
-        o = al(mb) + al(6 * H * W * bi)
-        st = al(3 * H * W * bo)
-        outs = [as_(ws[o + k * st:o + k * st + 3 * H * W * bo], bo, (3, H, W)) for k in range(n_t)]
-        return pair, outs
-
+    _yuv = _YUV
     to_planar = staticmethod(to_planar)
     from_planar = staticmethod(from_planar)
-
-    def forward_io(self, io, ws, stream=None):
-        """The raw call; returns the code without raising (tests of the error contract)."""
-        return lib().fldr_chroma_forward(self.model._h, ctypes.byref(io), ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
-                                         ws.numel() if ws is not None else 0, _stream_ptr(self.device, stream))
-
-    def _t(self, t):
-        """t as the float32 device tensor a forward reads: one that already is (contiguous, on a device) is used in place."""
-        if torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous():
-            return t
-        return torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device)
-
-    def make_io(self, frames, t, in_format, out_format, outs, H, W):
-        io = IO()
-        io.H, io.W = int(H), int(W)
-        io.in_format, io.out_format = in_format, out_format
-        for i, fr in enumerate(frames):
-            io.in_[i] = frame_struct(fr)
-        arr = (Frame * len(outs))(*[frame_struct(o) for o in outs])
-        io.n_t, io.t, io.out = len(outs), t.data_ptr(), ctypes.cast(arr, ctypes.POINTER(Frame))
-        io._keep = arr
-        return io
 
     def forward(self, frames, t=0.5, in_format=None, out_format=None, outs=None, ws=None, W=None, stream=None):
         """frames: (I0, I1), each a tuple of plane tensors in in_format; t: n_t values (a float32 device tensor is used in place: a
         captured call reads it at replay).  -> the n_t output frames (`outs` when given; allocated packed otherwise)."""
         in_format = in_format or Format()
-        out_format = out_format or in_format.copy()
         H, w = luma_size(frames[0], in_format)
-        W = w if W is None else W
-        tt = self._t(t)
-        n_t = tt.numel()
-        if outs is None:
-            outs = [empty_frame(out_format, H, W, self.device) for _ in range(n_t)]
-        if ws is None:
-            ws = self.workspace(H, W, n_t)
-        io = self.make_io(frames, tt, in_format, out_format, outs, H, W)
-        _check(self.forward_io(io, ws, stream), "fldr_chroma_forward")
-        return outs
+        return self._yuv_forward(frames, t, in_format, out_format, outs, ws, H, w if W is None else W, stream)
 
 
-class Session(HostStream):
+class Session(YuvSession):
     """fldr_chroma_session: host frames (tuples of numpy planes) pushed one by one; each push after the first returns n_t frames."""
 
-    _destroy = staticmethod(lambda h: lib().fldr_chroma_session_destroy(h))
-
-    def __init__(self, native_model, H, W, n_t=1, in_format=None, out_format=None, t=None):
-        in_format = in_format or Format()
-        out_format = out_format or in_format.copy()
-        cfg = SessionConfig()
-        cfg.H, cfg.W, cfg.n_t, cfg.device = int(H), int(W), int(n_t), native_model.device.index or 0
-        cfg.in_format, cfg.out_format = in_format, out_format
-        if t is not None:
-            ta = (ctypes.c_float * n_t)(*[float(v) for v in t])
-            cfg.t = ctypes.cast(ta, ctypes.POINTER(ctypes.c_float))
-        self._h = ctypes.c_void_p()
-        self.model = native_model                                    # the session uses the model: keep it alive
-        _check(lib().fldr_chroma_session_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_chroma_session_create")
-        self.H, self.W, self.n_t, self.in_format, self.out_format = int(H), int(W), int(n_t), in_format, out_format
-        self._outs = [tuple(np.empty(s, plane_dtype(out_format, numpy=True)) for s in plane_shapes(out_format, H, W)) for _ in range(n_t)]
-
-    def _out_structs(self):
-        return (Frame * len(self._outs))(*[frame_struct(o) for o in self._outs])
-
-    def push(self, frame):
-        """-> [] or a list of n_t output frames (tuples of numpy planes, fresh copies)."""
-        fr = frame_struct(frame)
-        n = ctypes.c_int(-1)
-        _check(lib().fldr_chroma_session_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n)), "fldr_chroma_session_push")
-        self.last_n_out = n.value
-        return self._taken(n.value)
-
-    def reset(self):
-        _check(lib().fldr_chroma_session_reset(self._h), "fldr_chroma_session_reset")
+    _yuv = _YUV

@@ -38,6 +38,9 @@ class Format(ctypes.Structure):
                          MATRICES[matrix] if isinstance(matrix, str) else matrix, RANGES[range] if isinstance(range, str) else range)
         self.depth = depth
 
+    def copy(self):
+        return Format(self.layout, self.matrix, self.range, self.depth)
+
     @property
     def depth(self):
         return int(self.reserved[0])
@@ -70,17 +73,22 @@ class SessionConfig(ctypes.Structure):
                 ("device", ctypes.c_int32), ("t", ctypes.POINTER(ctypes.c_float)), ("reserved", ctypes.c_int32 * 4)]
 
 
-_SIGNATURES = {
-    "fldr_video_version": (ctypes.c_int, []),
-    "fldr_video_error_string": (ctypes.c_char_p, [ctypes.c_int]),
-    "fldr_video_sizeof": (ctypes.c_int, [ctypes.c_int]),
-    "fldr_video_workspace_bytes": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
-    "fldr_video_forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IO), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
-    "fldr_video_session_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SessionConfig), ctypes.POINTER(ctypes.c_void_p)]),
-    "fldr_video_session_push": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.POINTER(Frame), ctypes.POINTER(ctypes.c_int)]),
-    "fldr_video_session_reset": (ctypes.c_int, [ctypes.c_void_p]),
-    "fldr_video_session_destroy": (None, [ctypes.c_void_p]),
-}
+def yuv_signatures(prefix, Frame, IO, SessionConfig):
+    """The functions every YUV library on the model exports (fldr_video.h, fldr_chroma.h), as fldr_model.load_library takes them."""
+    return {
+        prefix + "version": (ctypes.c_int, []),
+        prefix + "error_string": (ctypes.c_char_p, [ctypes.c_int]),
+        prefix + "sizeof": (ctypes.c_int, [ctypes.c_int]),
+        prefix + "workspace_bytes": (ctypes.c_int64, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+        prefix + "forward": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(IO), ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p]),
+        prefix + "session_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(SessionConfig), ctypes.POINTER(ctypes.c_void_p)]),
+        prefix + "session_push": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Frame), ctypes.POINTER(Frame), ctypes.POINTER(ctypes.c_int)]),
+        prefix + "session_reset": (ctypes.c_int, [ctypes.c_void_p]),
+        prefix + "session_destroy": (None, [ctypes.c_void_p]),
+    }
+
+
+_SIGNATURES = yuv_signatures("fldr_video_", Frame, IO, SessionConfig)
 EXPORTS = tuple(_SIGNATURES)
 _lib = None
 # libfldr_video_test.so (-DFLDR_TEST_HOOKS): the same sources + the converter hooks of include/fldr_video_test_hooks.h; tests only
@@ -198,18 +206,45 @@ def debug_last_path():
     return int(test_hooks().fldr_video_debug_last_path())
 
 
-class NativeVideo:
-    """YUV forwards on a fldr_model.NativeModel (read-only: forwards on several streams, each with its own workspace, may run at once)."""
+class YuvApi:
+    """One YUV library on the model, as YuvNative and YuvSession use it: its handle (`lib`, a function), the `fldr_<name>_` prefix of its
+    functions, its error class, its struct classes and the geometry functions of its frames."""
+
+    def __init__(self, lib, prefix, error, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype):
+        self.lib, self.prefix, self.error = lib, prefix, error
+        self.Format, self.Frame, self.IO, self.SessionConfig = Format, Frame, IO, SessionConfig
+        self.frame_struct, self.plane_shapes, self.plane_dtype = frame_struct, plane_shapes, plane_dtype
+
+    def fn(self, name):
+        return getattr(self.lib(), self.prefix + name)
+
+    def check(self, code, name):
+        if code != 0:
+            raise self.error(self.prefix + name, code)
+
+    def empty_frame(self, fmt, H, W, device):
+        return tuple(torch.empty(r, c, dtype=self.plane_dtype(fmt), device=device) for r, c in self.plane_shapes(fmt, H, W))
+
+    def frame_array(self, frames):
+        return (self.Frame * len(frames))(*[self.frame_struct(f) for f in frames])
+
+
+_YUV = YuvApi(lib, "fldr_video_", VideoError, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype)
+
+
+class YuvNative:
+    """YUV forwards of the library `_yuv` (a YuvApi) on a fldr_model.NativeModel; a subclass names the library and gives `forward` its
+    signature."""
 
     def __init__(self, native_model):
-        lib()
+        self._yuv.lib()
         self.model = native_model
         self.device = native_model.device
 
     def workspace_bytes(self, H, W, n_t=1):
-        n = lib().fldr_video_workspace_bytes(self.model._h, int(H), int(W), int(n_t))
+        n = self._yuv.fn("workspace_bytes")(self.model._h, int(H), int(W), int(n_t))
         if n < 0:
-            raise VideoError("fldr_video_workspace_bytes", int(n))
+            raise self._yuv.error(self._yuv.prefix + "workspace_bytes", int(n))
         return int(n)
 
     def workspace(self, H, W, n_t=1):
@@ -230,8 +265,8 @@ class NativeVideo:
 
     def forward_io(self, io, ws, stream=None):
         """The raw call; returns the code without raising (tests of the error contract)."""
-        return lib().fldr_video_forward(self.model._h, ctypes.byref(io), ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
-                                        ws.numel() if ws is not None else 0, _stream_ptr(self.device, stream))
+        return self._yuv.fn("forward")(self.model._h, ctypes.byref(io), ctypes.c_void_p(ws.data_ptr()) if ws is not None else None,
+                                       ws.numel() if ws is not None else 0, _stream_ptr(self.device, stream))
 
     def _t(self, t):
         """t as the float32 device tensor a forward reads: one that already is (contiguous, on a device) is used in place."""
@@ -240,43 +275,54 @@ class NativeVideo:
         return torch.as_tensor(t, dtype=torch.float32).reshape(-1).to(self.device)
 
     def make_io(self, frames, t, in_format, out_format, outs, H, W):
-        io = IO()
+        io = self._yuv.IO()
         io.H, io.W = int(H), int(W)
         io.in_format, io.out_format = in_format, out_format
         for i, fr in enumerate(frames):
-            io.in_[i] = frame_struct(fr)
-        arr = (Frame * len(outs))(*[frame_struct(o) for o in outs])
-        io.n_t, io.t, io.out = len(outs), t.data_ptr(), ctypes.cast(arr, ctypes.POINTER(Frame))
+            io.in_[i] = self._yuv.frame_struct(fr)
+        arr = self._yuv.frame_array(outs)
+        io.n_t, io.t, io.out = len(outs), t.data_ptr(), ctypes.cast(arr, ctypes.POINTER(self._yuv.Frame))
         io._keep = arr
         return io
+
+    def _yuv_forward(self, frames, t, in_format, out_format, outs, ws, H, W, stream):
+        """What a subclass's forward does once it knows its formats and the frame size."""
+        in_format = in_format or self._yuv.Format()
+        out_format = out_format or in_format.copy()
+        tt = self._t(t)
+        n_t = tt.numel()
+        if outs is None:
+            outs = [self._yuv.empty_frame(out_format, H, W, self.device) for _ in range(n_t)]
+        if ws is None:
+            ws = self.workspace(H, W, n_t)
+        io = self.make_io(frames, tt, in_format, out_format, outs, H, W)
+        self._yuv.check(self.forward_io(io, ws, stream), "forward")
+        return outs
+
+
+class NativeVideo(YuvNative):
+    """YUV forwards on a fldr_model.NativeModel (read-only: forwards on several streams, each with its own workspace, may run at once)."""
+
+    _yuv = _YUV
 
     def forward(self, frames, t=0.5, in_format=None, out_format=None, outs=None, ws=None, stream=None):
         """frames: (I0, I1), each a tuple of plane tensors in in_format; t: n_t values (a float32 device tensor is used in place: a
         captured call reads it at replay).  -> the n_t output frames (`outs` when given; allocated packed otherwise)."""
-        in_format = in_format or Format()
-        out_format = out_format or Format(in_format.layout, in_format.matrix, in_format.range, in_format.depth)
         H, W = frames[0][0].shape
-        tt = self._t(t)
-        n_t = tt.numel()
-        if outs is None:
-            outs = [empty_frame(out_format, H, W, self.device) for _ in range(n_t)]
-        if ws is None:
-            ws = self.workspace(H, W, n_t)
-        io = self.make_io(frames, tt, in_format, out_format, outs, H, W)
-        _check(self.forward_io(io, ws, stream), "fldr_video_forward")
-        return outs
+        return self._yuv_forward(frames, t, in_format, out_format, outs, ws, H, W, stream)
 
 
 class HostStream:
     """What Session and fldr_rate.Converter share: the lifetime of the handle `_h` (a subclass names the library's `_destroy`) and the
-    host planes the library writes a push's output frames into."""
+    host planes the library writes a push's output frames into (frames of the library `_yuv`: 4:2:0 unless a subclass says otherwise)."""
     _h = None
+    _yuv = _YUV
 
     def _stage(self, fmt, H, W, n):
-        self._outs = [tuple(np.empty(s, plane_dtype(fmt, numpy=True)) for s in plane_shapes(fmt, H, W)) for _ in range(n)]
+        self._outs = [tuple(np.empty(s, self._yuv.plane_dtype(fmt, numpy=True)) for s in self._yuv.plane_shapes(fmt, H, W)) for _ in range(n)]
 
     def _out_structs(self):
-        return (Frame * len(self._outs))(*[frame_struct(o) for o in self._outs])
+        return self._yuv.frame_array(self._outs)
 
     def _taken(self, n):
         """The first n staged frames as fresh copies."""
@@ -294,15 +340,17 @@ class HostStream:
             pass
 
 
-class Session(HostStream):
-    """fldr_video_session: host frames (tuples of numpy planes) pushed one by one; each push after the first returns n_t frames."""
+class YuvSession(HostStream):
+    """The session of the library `_yuv`: host frames (tuples of numpy planes) pushed one by one; each push after the first returns n_t
+    frames."""
 
-    _destroy = staticmethod(lambda h: lib().fldr_video_session_destroy(h))
+    def _destroy(self, h):
+        self._yuv.fn("session_destroy")(h)
 
     def __init__(self, native_model, H, W, n_t=1, in_format=None, out_format=None, t=None):
-        in_format = in_format or Format()
-        out_format = out_format or Format(in_format.layout, in_format.matrix, in_format.range, in_format.depth)
-        cfg = SessionConfig()
+        in_format = in_format or self._yuv.Format()
+        out_format = out_format or in_format.copy()
+        cfg = self._yuv.SessionConfig()
         cfg.H, cfg.W, cfg.n_t, cfg.device = int(H), int(W), int(n_t), native_model.device.index or 0
         cfg.in_format, cfg.out_format = in_format, out_format
         if t is not None:
@@ -310,17 +358,22 @@ class Session(HostStream):
             cfg.t = ctypes.cast(ta, ctypes.POINTER(ctypes.c_float))
         self._h = ctypes.c_void_p()
         self.model = native_model                                    # the session uses the model: keep it alive
-        _check(lib().fldr_video_session_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_video_session_create")
+        self._yuv.check(self._yuv.fn("session_create")(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "session_create")
         self.H, self.W, self.n_t, self.in_format, self.out_format = int(H), int(W), int(n_t), in_format, out_format
         self._stage(out_format, H, W, n_t)
 
     def push(self, frame):
         """-> [] or a list of n_t output frames (tuples of numpy planes, fresh copies)."""
-        fr = frame_struct(frame)
+        fr = self._yuv.frame_struct(frame)
         n = ctypes.c_int(-1)
-        _check(lib().fldr_video_session_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n)), "fldr_video_session_push")
+        self._yuv.check(self._yuv.fn("session_push")(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n)), "session_push")
         self.last_n_out = n.value
         return self._taken(n.value)
 
     def reset(self):
-        _check(lib().fldr_video_session_reset(self._h), "fldr_video_session_reset")
+        self._yuv.check(self._yuv.fn("session_reset")(self._h), "session_reset")
+
+
+class Session(YuvSession):
+    """fldr_video_session: host frames (tuples of numpy planes) pushed one by one; each push after the first returns n_t frames."""
+

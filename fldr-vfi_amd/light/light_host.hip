@@ -98,13 +98,11 @@ Tables tables_of(const fldr_light_curve* c) {
 const YuvCoeffs& coeffs(const fldr_video_format& f) { return deep(f) ? YUV_COEFFS_10[f.matrix][f.range] : YUV_COEFFS[f.matrix][f.range]; }
 
 int to_planar(const Plan& p, const fldr_video_frame in[2], void* pair, hipStream_t s) {
-    if (p.deep) return yuv420_to_planar_pair10(in, p.fmt.layout, coeffs(p.fmt), (uint16_t*)pair, p.H, p.W, s);
-    return yuv420_to_planar_pair(in, p.fmt.layout, coeffs(p.fmt), (uint8_t*)pair, p.H, p.W, s);
+    return yuv420_to_planar_pair(in, p.fmt, coeffs(p.fmt), pair, p.H, p.W, s);
 }
 
 int from_planar(const Plan& p, const void* planar, const fldr_video_frame& out, hipStream_t s) {
-    if (p.deep) return planar_to_yuv420_10((const uint16_t*)planar, out, p.fmt.layout, coeffs(p.fmt), p.H, p.W, s);
-    return planar_to_yuv420((const uint8_t*)planar, out, p.fmt.layout, coeffs(p.fmt), p.H, p.W, s);
+    return planar_to_yuv420(planar, out, p.fmt, coeffs(p.fmt), p.H, p.W, s);
 }
 
 bool aligned16(const Sources& s) {

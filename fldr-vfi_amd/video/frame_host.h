@@ -1,8 +1,9 @@
 // The host side of the frame contract of include/fldr_video.h (what a valid format and a valid frame are, how large a plane is) and the
 // plumbing of a stream object (fldr_video_session, fldr_rate): a device, a stream, one device block, one pinned block, packed frames in
-// them.  Included by video_host.hip, by the shutter and light libraries' host files and, through ../rate/rate_plan.h, by the rate, pipe
-// and cadence libraries': each refuses exactly the frames libfldr_video.so refuses because all compile this text.  Everything is in
-// the unnamed namespace: nothing here becomes a symbol of any library.
+// them.  Included by video_host.hip and ../chroma/chroma_host.hip (through yuv_stream_host.h), by the shutter and light libraries' host
+// files and, through ../rate/rate_plan.h, by the rate, pipe and cadence libraries': each refuses exactly the frames libfldr_video.so
+// refuses because all compile this text (the chroma library with its own FrameRules, below).  Everything is in the unnamed namespace:
+// nothing here becomes a symbol of any library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -21,7 +22,7 @@ int64_t align_up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 // ---- formats and frames -----------------------------------------------------------------------------------------------------------
 int planes_of(int layout) { return layout == FLDR_VIDEO_NV12 ? 2 : 3; }
 
-bool deep(const fldr_video_format& f) { return f.depth == 10; }       // 16-bit words (depth 0 is an alias of 8)
+template <class Format> bool deep(const Format& f) { return f.depth == 10; }       // 16-bit words (depth 0 is an alias of 8)
 
 int check_format(const fldr_video_format& f) {
     if ((unsigned)f.layout > 1u || (unsigned)f.matrix > 1u || (unsigned)f.range > 1u) return FLDR_VIDEO_E_FORMAT;
@@ -38,37 +39,55 @@ int64_t row_bytes(const fldr_video_format& f, int p, int W) {
 
 int rows_of(int p, int H) { return p == 0 ? H : (H + 1) / 2; }
 
-int check_frame(const fldr_video_frame& fr, const fldr_video_format& f, int W) {
-    for (int p = 0; p < planes_of(f.layout); ++p) if (!fr.plane[p] || (deep(f) && ((uintptr_t)fr.plane[p] & 1))) return FLDR_VIDEO_E_PLANE;
-    for (int p = 0; p < planes_of(f.layout); ++p)
-        if (fr.pitch[p] < row_bytes(f, p, W) || (deep(f) && (fr.pitch[p] & 1))) return FLDR_VIDEO_E_PITCH;
+// The functions below are written once for every YUV format struct (a `depth` word: 10 = 16-bit samples, and frames of plane[3] /
+// pitch[3]).  A library states its own rules in a FrameRules<Format>: the frame type, its E_PLANE / E_PITCH codes, the planes of a
+// format, the bytes per row and the rows of plane p.  These are fldr_video.h's (4:2:0); ../chroma/chroma_host.hip has the other.
+template <class Format> struct FrameRules;
+template <> struct FrameRules<fldr_video_format> {
+    using Frame = fldr_video_frame;
+    static constexpr int E_PLANE = FLDR_VIDEO_E_PLANE, E_PITCH = FLDR_VIDEO_E_PITCH;
+    static int planes(const fldr_video_format& f) { return planes_of(f.layout); }
+    static int64_t row_bytes(const fldr_video_format& f, int p, int W) { return ::row_bytes(f, p, W); }
+    static int rows(const fldr_video_format&, int p, int H) { return rows_of(p, H); }
+};
+template <class Format> using FrameOf = typename FrameRules<Format>::Frame;
+
+template <class Format> int check_frame(const FrameOf<Format>& fr, const Format& f, int W) {
+    using R = FrameRules<Format>;
+    const bool words = f.depth == 10;
+    for (int p = 0; p < R::planes(f); ++p) if (!fr.plane[p] || (words && ((uintptr_t)fr.plane[p] & 1))) return R::E_PLANE;
+    for (int p = 0; p < R::planes(f); ++p)
+        if (fr.pitch[p] < R::row_bytes(f, p, W) || (words && (fr.pitch[p] & 1))) return R::E_PITCH;
     return 0;
 }
 
 // ---- packed frames ----------------------------------------------------------------------------------------------------------------
 // packed planes of one frame (pitch = row bytes) starting at `base`
-fldr_video_frame packed(uint8_t* base, const fldr_video_format& fmt, int H, int W) {
-    fldr_video_frame f;
+template <class Format> FrameOf<Format> packed(uint8_t* base, const Format& fmt, int H, int W) {
+    using R = FrameRules<Format>;
+    FrameOf<Format> f;
     memset(&f, 0, sizeof(f));
     int64_t off = 0;
-    for (int p = 0; p < planes_of(fmt.layout); ++p) {
+    for (int p = 0; p < R::planes(fmt); ++p) {
         f.plane[p] = base + off;
-        f.pitch[p] = row_bytes(fmt, p, W);
-        off += f.pitch[p] * rows_of(p, H);
+        f.pitch[p] = R::row_bytes(fmt, p, W);
+        off += f.pitch[p] * R::rows(fmt, p, H);
     }
     return f;
 }
 
-int64_t packed_bytes(const fldr_video_format& fmt, int H, int W) {
+template <class Format> int64_t packed_bytes(const Format& fmt, int H, int W) {
+    using R = FrameRules<Format>;
     int64_t n = 0;
-    for (int p = 0; p < planes_of(fmt.layout); ++p) n += row_bytes(fmt, p, W) * rows_of(p, H);
+    for (int p = 0; p < R::planes(fmt); ++p) n += R::row_bytes(fmt, p, W) * R::rows(fmt, p, H);
     return n;
 }
 
 // rows of every plane from `src` (any pitches) to `dst` (any pitches), on the host
-void copy_planes(const fldr_video_frame& dst, const fldr_video_frame& src, const fldr_video_format& fmt, int H, int W) {
-    for (int p = 0; p < planes_of(fmt.layout); ++p) {
-        const int64_t rb = row_bytes(fmt, p, W), n = rows_of(p, H);
+template <class Format> void copy_planes(const FrameOf<Format>& dst, const FrameOf<Format>& src, const Format& fmt, int H, int W) {
+    using R = FrameRules<Format>;
+    for (int p = 0; p < R::planes(fmt); ++p) {
+        const int64_t rb = R::row_bytes(fmt, p, W), n = R::rows(fmt, p, H);
         for (int64_t r = 0; r < n; ++r)
             memcpy((uint8_t*)dst.plane[p] + r * dst.pitch[p], (const uint8_t*)src.plane[p] + r * src.pitch[p], (size_t)rb);
     }
@@ -115,14 +134,15 @@ bool open_stream_mem(StreamMem& m, int device, int64_t dev_bytes, int64_t pinned
 }
 
 // one host frame (any pitches) -> packed in `pinned_slot` -> enqueued to `dev_slot`; the pinned copy stays valid for the caller
-hipError_t upload_frame(const StreamMem& m, uint8_t* dev_slot, uint8_t* pinned_slot, int64_t slot_bytes, const fldr_video_frame& src,
-                        const fldr_video_format& fmt, int H, int W) {
+template <class Format>
+hipError_t upload_frame(const StreamMem& m, uint8_t* dev_slot, uint8_t* pinned_slot, int64_t slot_bytes, const FrameOf<Format>& src,
+                        const Format& fmt, int H, int W) {
     copy_planes(packed(pinned_slot, fmt, H, W), src, fmt, H, W);
     return hipMemcpyAsync(dev_slot, pinned_slot, (size_t)slot_bytes, hipMemcpyHostToDevice, m.stream);
 }
 
 // one packed frame in the pinned block -> the caller's planes
-void unpack_frame(const fldr_video_frame& dst, uint8_t* pinned_slot, const fldr_video_format& fmt, int H, int W) {
+template <class Format> void unpack_frame(const FrameOf<Format>& dst, uint8_t* pinned_slot, const Format& fmt, int H, int W) {
     copy_planes(dst, packed(pinned_slot, fmt, H, W), fmt, H, W);
 }
 

@@ -135,10 +135,13 @@ def _no_stale_half_packing(lib):
     import kernel_resources as KR
     n, seen = 0, False
     for txt in _disassemble(lib):
-        seen = seen or ("yuv420_to_planar_pair10_kernel" in txt and "planar_to_yuv420_10_kernel" in txt)
+        # both kernels in both sample types: Ih / It open the mangled template arguments <unsigned char, ...> / <unsigned short, ...>
+        seen = seen or all(k + t in txt for k in ("yuv420_to_planar_pair_kernelI", "planar_to_yuv420_kernelI") for t in "ht")
         n += len(re.findall(r"\bv_ashr_pk_\w+|\bv_cvt_pk_[ui]16_\w+", txt))
     assert seen and n == 0
-    for k in KR.kernels(lib):
+    ks = KR.kernels(lib)
+    assert sum("yuv420" in k["name"] for k in ks) == 16                        # 2 kernels x 2 sample types x 2 layouts x 2 forms
+    for k in ks:
         assert k["scratch"] == 0 and k["vgpr_spills"] == 0, k
 
 

@@ -149,7 +149,7 @@ def test_no_ashr_pk_in_the_video_test_library():
 def test_hook_sources_stay_out_of_the_product_build():
     """Everything the test build adds sits behind FLDR_TEST_HOOKS: with the macro undefined the preprocessor drops every line that names
     a hook, so libfldr_video.so is compiled from the text it was compiled from before the hooks existed."""
-    for name in ("video_host.hip", "video_kernels.hip", "video_internal.h", "frame_host.h"):
+    for name in ("video_host.hip", "video_kernels.hip", "video_internal.h", "frame_host.h", "yuv_stream_host.h", "yuv_run_device.h"):
         depth, live = [], []
         for line in open(os.path.join(PKG, "video", name)).read().splitlines():
             t = line.strip()
