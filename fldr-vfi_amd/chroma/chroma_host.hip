@@ -1,4 +1,4 @@
-// libfldr_chroma.so, host side: what a valid fldr_chroma_format is and how large its planes are, the two public converters, and what the
+// libfldr_chroma.so, host side: what a valid fldr_chroma_format is and how large its planes are, and what the
 // library puts into the one forward and session text of ../video/yuv_stream_host.h (its structs, codes, format check, colour constants and
 // converters), its error strings, and the exported functions as wrappers.  The frame checks, packed frames and the stream / device block
 // / pinned block of a session come from ../video/frame_host.h, the colour tables from ../video/yuv_color.h, so all are those of
@@ -34,21 +34,23 @@ template <> struct FrameRules<fldr_chroma_format> {
         return b * (p == 0 ? W : (f.layout == FLDR_CHROMA_SEMIPLANAR ? 2 * cw : cw));
     }
     static int rows(const fldr_chroma_format&, int, int H) { return H; }      // no vertical subsampling
+    static int unit(const fldr_chroma_format&) { return 0; }
 };
 
 const YuvCoeffs& coeffs(const fldr_chroma_format& f) {
     return deep(f) ? fldr_video_impl::YUV_COEFFS_10[f.matrix][f.range] : fldr_video_impl::YUV_COEFFS[f.matrix][f.range];
 }
 
-struct ChromaLib {
+struct ChromaLib : LibDefaults {
     using Format = fldr_chroma_format;
     using Frame = fldr_chroma_frame;
     using Io = fldr_chroma_io;
     using Config = fldr_chroma_session_config;
     static constexpr int E_ARG = FLDR_CHROMA_E_ARG, E_FORMAT = FLDR_CHROMA_E_FORMAT, E_WORKSPACE = FLDR_CHROMA_E_WORKSPACE, E_DEVICE = FLDR_CHROMA_E_DEVICE;
+    static constexpr int MAX_FRAMES = fldr_chroma_impl::MAX_FRAMES;
     static int check_format(const Format& f) { return ::check_format(f); }
-    static int to_planar(const Frame in[2], const Format& f, void* pair, int H, int W, hipStream_t s) {
-        return fldr_chroma_impl::to_planar(in, 2, f, coeffs(f), pair, H, W, s);
+    static int to_planar(const Frame* in, int n, const Format& f, void* planar, int H, int W, hipStream_t s) {
+        return fldr_chroma_impl::to_planar(in, n, f, coeffs(f), planar, H, W, s);
     }
     static int from_planar(const void* planar, const Frame& out, const Format& f, int H, int W, hipStream_t s) {
         return fldr_chroma_impl::from_planar(planar, out, f, coeffs(f), H, W, s);
@@ -70,42 +72,20 @@ extern "C" FLDR_CHROMA_API const char* fldr_chroma_error_string(int code) {
     case FLDR_CHROMA_E_PLANE: return "fldr_chroma: null plane pointer (or an odd address at depth 10)";
     case FLDR_CHROMA_E_WORKSPACE: return "fldr_chroma: workspace missing, misaligned or too small";
     case FLDR_CHROMA_E_DEVICE: return "fldr_chroma: no such device or out of memory";
-    default: return code > -100 && code < 0 ? fldr_model_error_string(code) : code > 0 ? hipGetErrorString((hipError_t)code)
-                                                                                      : "fldr_chroma: unknown error";
+    default: return passed_error_string(code, "fldr_chroma: unknown error");
     }
 }
 
-extern "C" FLDR_CHROMA_API int fldr_chroma_sizeof(int which) {
-    switch (which) {
-    case 0: return (int)sizeof(fldr_chroma_format);
-    case 1: return (int)sizeof(fldr_chroma_frame);
-    case 2: return (int)sizeof(fldr_chroma_io);
-    case 3: return (int)sizeof(fldr_chroma_session_config);
-    default: return FLDR_CHROMA_E_ARG;
-    }
-}
+extern "C" FLDR_CHROMA_API int fldr_chroma_sizeof(int which) { return struct_sizeof<ChromaLib>(which); }
 
 extern "C" FLDR_CHROMA_API int fldr_chroma_to_planar(const fldr_chroma_frame* frames, int n_frames, const fldr_chroma_format* format, void* planar,
                                                      int H, int W, void* stream) {
-    if (!frames || !format || !planar || n_frames < 1 || H < 1 || W < 1) return FLDR_CHROMA_E_ARG;
-    CK(check_format(*format));
-    if (deep(*format) && ((uintptr_t)planar & 1)) return FLDR_CHROMA_E_ARG;
-    for (int f = 0; f < n_frames; ++f) CK(check_frame(frames[f], *format, W));
-    const int64_t frame_bytes = 3ll * H * W * (deep(*format) ? 2 : 1);
-    for (int f = 0; f < n_frames; f += MAX_FRAMES) {
-        const int n = n_frames - f < MAX_FRAMES ? n_frames - f : MAX_FRAMES;
-        CK(to_planar(frames + f, n, *format, coeffs(*format), (uint8_t*)planar + f * frame_bytes, H, W, (hipStream_t)stream));
-    }
-    return 0;
+    return to_planar_entry<ChromaLib>(frames, n_frames, format, planar, H, W, stream);
 }
 
 extern "C" FLDR_CHROMA_API int fldr_chroma_from_planar(const void* planar, const fldr_chroma_format* format, const fldr_chroma_frame* out_frame,
                                                        int H, int W, void* stream) {
-    if (!planar || !format || !out_frame || H < 1 || W < 1) return FLDR_CHROMA_E_ARG;
-    CK(check_format(*format));
-    if (deep(*format) && ((uintptr_t)planar & 1)) return FLDR_CHROMA_E_ARG;
-    CK(check_frame(*out_frame, *format, W));
-    return from_planar(planar, *out_frame, *format, coeffs(*format), H, W, (hipStream_t)stream);
+    return from_planar_entry<ChromaLib>(planar, format, out_frame, H, W, stream);
 }
 
 extern "C" FLDR_CHROMA_API int64_t fldr_chroma_workspace_bytes(const fldr_model* m, int H, int W, int n_t) { return workspace_bytes<ChromaLib>(m, H, W, n_t); }

@@ -164,7 +164,6 @@ __global__ __launch_bounds__(CK_TX * CK_TY) void chroma_from_planar_kernel(OutAr
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
-static bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 static int planes_used(int layout) { return layout == FLDR_CHROMA_PLANAR ? 3 : layout == FLDR_CHROMA_SEMIPLANAR ? 2 : 1; }
 
 // Call GO(S, L) for the (sampling, layout) of `fmt`; the packed layouts exist for bytes at 4:2:2 only (the caller checked the format).
@@ -187,25 +186,20 @@ static int to_planar_t(const fldr_chroma_frame* in, int n, const fldr_chroma_for
     constexpr int R = RUN<T>;
     InArgs a;
     const int np = planes_used(fmt.layout);
-    bool vec = W % R == 0 && al16(planar);
+    bool vec = W % R == 0 && al(planar, 16);
     for (int f = 0; f < MAX_FRAMES; ++f)
         for (int p = 0; p < 3; ++p) {
             const bool used = f < n && p < np;
             a.plane[f][p] = used ? (const uint8_t*)in[f].plane[p] : nullptr;
             a.pitch[f][p] = used ? in[f].pitch[p] : 0;
-            if (used) vec = vec && al16(in[f].plane[p]) && (in[f].pitch[p] & 15) == 0;
+            if (used) vec = vec && al(in[f].plane[p], 16) && al(in[f].pitch[p], 16);
         }
     a.dst = (uint8_t*)planar; a.H = H; a.W = W; a.k = k;
-    const dim3 grid(((W + R - 1) / R + CK_TX - 1) / CK_TX, (H + CK_TY - 1) / CK_TY, n), block(CK_TX, CK_TY);
-#define GO(S, L)                                                                                          \
-    do {                                                                                                  \
-        if (vec) hipLaunchKernelGGL((chroma_to_planar_kernel<T, S, L, true>), grid, block, 0, stream, a); \
-        else hipLaunchKernelGGL((chroma_to_planar_kernel<T, S, L, false>), grid, block, 0, stream, a);    \
-    } while (0)
+    const dim3 grid = row_grid<CK_TX, CK_TY>(R, H, W, n), block(CK_TX, CK_TY);
+#define GO(S, L) YUV_LAUNCH_VEC(chroma_to_planar_kernel, vec, grid, block, stream, a, T, S, L)
     CK_DISPATCH(T, fmt);
 #undef GO
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launched();
 }
 
 template <typename T>
@@ -214,23 +208,18 @@ static int from_planar_t(const void* planar, const fldr_chroma_frame& out, const
     constexpr int R = RUN<T>;
     OutArgs a;
     const int np = planes_used(fmt.layout);
-    bool vec = W % R == 0 && al16(planar);
+    bool vec = W % R == 0 && al(planar, 16);
     for (int p = 0; p < 3; ++p) {
         a.plane[p] = p < np ? (uint8_t*)out.plane[p] : nullptr;
         a.pitch[p] = p < np ? out.pitch[p] : 0;
-        if (p < np) vec = vec && al16(out.plane[p]) && (out.pitch[p] & 15) == 0;
+        if (p < np) vec = vec && al(out.plane[p], 16) && al(out.pitch[p], 16);
     }
     a.src = (const uint8_t*)planar; a.H = H; a.W = W; a.k = k;
-    const dim3 grid(((W + R - 1) / R + CK_TX - 1) / CK_TX, (H + CK_TY - 1) / CK_TY, 1), block(CK_TX, CK_TY);
-#define GO(S, L)                                                                                            \
-    do {                                                                                                    \
-        if (vec) hipLaunchKernelGGL((chroma_from_planar_kernel<T, S, L, true>), grid, block, 0, stream, a); \
-        else hipLaunchKernelGGL((chroma_from_planar_kernel<T, S, L, false>), grid, block, 0, stream, a);    \
-    } while (0)
+    const dim3 grid = row_grid<CK_TX, CK_TY>(R, H, W, 1), block(CK_TX, CK_TY);
+#define GO(S, L) YUV_LAUNCH_VEC(chroma_from_planar_kernel, vec, grid, block, stream, a, T, S, L)
     CK_DISPATCH(T, fmt);
 #undef GO
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launched();
 }
 
 int to_planar(const fldr_chroma_frame* in, int n, const fldr_chroma_format& fmt, const YuvCoeffs& k, void* planar, int H, int W, hipStream_t stream) {

@@ -17,8 +17,8 @@ import os
 import numpy as np
 import torch
 
-import fldr_model
-from fldr_video import YuvApi, YuvNative, YuvSession, _stream_ptr, frame_struct as _video_frame_struct, yuv_signatures
+from fldr_video import (YuvApi, YuvError, YuvNative, YuvSession, converter_signatures, frame_struct as _video_frame_struct, yuv_signatures,
+                        yuv_structs)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfldr_chroma.so")
@@ -53,44 +53,13 @@ class Frame(ctypes.Structure):
     _fields_ = [("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
 
 
-class IO(ctypes.Structure):
-    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("in_", Frame * 2), ("out_format", Format),
-                ("n_t", ctypes.c_int32), ("t", ctypes.c_void_p), ("out", ctypes.POINTER(Frame))]
-
-
-class SessionConfig(ctypes.Structure):
-    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("out_format", Format), ("n_t", ctypes.c_int32),
-                ("device", ctypes.c_int32), ("t", ctypes.POINTER(ctypes.c_float)), ("reserved", ctypes.c_int32 * 4)]
-
-
-_SIGNATURES = {
-    **yuv_signatures("fldr_chroma_", Frame, IO, SessionConfig),
-    "fldr_chroma_to_planar": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.c_int, ctypes.POINTER(Format), ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_void_p]),
-    "fldr_chroma_from_planar": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Format), ctypes.POINTER(Frame), ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_void_p]),
-}
+IO, SessionConfig = yuv_structs(Format, Frame)
+_SIGNATURES = {**yuv_signatures("fldr_chroma_", Frame, IO, SessionConfig), **converter_signatures("fldr_chroma_", Format, Frame)}
 EXPORTS = tuple(_SIGNATURES)
-_lib = None
 
 
-class ChromaError(RuntimeError):
-    def __init__(self, what, code):
-        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_chroma_error_string(code).decode(), code))
-        self.code = code
-
-
-def lib():
-    """The loaded libfldr_chroma.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (Format, Frame, IO, SessionConfig), "fldr_chroma", CHROMA_VERSION)
-    return _lib
-
-
-def _check(code, what):
-    if code != 0:
-        raise ChromaError(what, code)
+class ChromaError(YuvError):
+    pass
 
 
 # ---- geometry ---------------------------------------------------------------------------------------------------------------------
@@ -119,8 +88,8 @@ def frame_struct(planes):
     return f
 
 
-_YUV = YuvApi(lib, "fldr_chroma_", ChromaError, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype)
-empty_frame = _YUV.empty_frame
+_YUV = YuvApi("chroma", LIB_PATH, CHROMA_VERSION, ChromaError, _SIGNATURES, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype)
+lib, empty_frame = _YUV.lib, _YUV.empty_frame
 
 
 def luma_size(frame, fmt):
@@ -134,27 +103,13 @@ def to_planar(frames, fmt, planar=None, W=None, stream=None):
     """fldr_chroma_to_planar: a list of frames in `fmt` (tuples of device plane tensors, pitches from their strides) -> planar BGR
     [n,3,H,W] (uint8; uint16 at depth 10; `planar` when given).  W: the luma width of a packed frame when it is odd."""
     H, w = luma_size(frames[0], fmt)
-    W = w if W is None else W
-    device = frames[0][0].device
-    if planar is None:
-        planar = torch.empty(len(frames), 3, H, W, dtype=plane_dtype(fmt), device=device)
-    arr = (Frame * len(frames))(*[frame_struct(f) for f in frames])
-    _check(lib().fldr_chroma_to_planar(arr, len(frames), ctypes.byref(fmt), ctypes.c_void_p(planar.data_ptr()), int(H), int(W),
-                                       _stream_ptr(device, stream)), "fldr_chroma_to_planar")
-    return planar
+    return _YUV.to_planar(frames, fmt, H, w if W is None else W, planar, stream)
 
 
 def from_planar(planar, fmt, out=None, stream=None):
     """fldr_chroma_from_planar: a planar BGR device tensor [3,H,W] with contiguous rows and planes (uint8; uint16 at depth 10) -> one
     frame in `fmt` (`out`: a tuple of plane tensors, pitches from their strides; allocated packed otherwise)."""
-    _, H, W = planar.shape
-    assert planar.is_contiguous() and planar.dtype == plane_dtype(fmt)
-    if out is None:
-        out = empty_frame(fmt, H, W, planar.device)
-    fr = frame_struct(out)
-    _check(lib().fldr_chroma_from_planar(ctypes.c_void_p(planar.data_ptr()), ctypes.byref(fmt), ctypes.byref(fr), int(H), int(W),
-                                         _stream_ptr(planar.device, stream)), "fldr_chroma_from_planar")
-    return out
+    return _YUV.from_planar(planar, fmt, out, stream)
 
 
 class NativeChroma(YuvNative):

@@ -18,8 +18,7 @@ import os
 import numpy as np
 import torch
 
-import fldr_model
-from fldr_video import YuvApi, YuvNative, YuvSession, _stream_ptr, yuv_signatures
+from fldr_video import YuvApi, YuvError, YuvNative, YuvSession, converter_signatures, yuv_signatures, yuv_structs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfldr_pack10.so")
@@ -56,44 +55,13 @@ class Frame(ctypes.Structure):
     _fields_ = [("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
 
 
-class IO(ctypes.Structure):
-    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("in_", Frame * 2), ("out_format", Format),
-                ("n_t", ctypes.c_int32), ("t", ctypes.c_void_p), ("out", ctypes.POINTER(Frame))]
-
-
-class SessionConfig(ctypes.Structure):
-    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("out_format", Format), ("n_t", ctypes.c_int32),
-                ("device", ctypes.c_int32), ("t", ctypes.POINTER(ctypes.c_float)), ("reserved", ctypes.c_int32 * 4)]
-
-
-_SIGNATURES = {
-    **yuv_signatures("fldr_pack10_", Frame, IO, SessionConfig),
-    "fldr_pack10_to_planar": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.c_int, ctypes.POINTER(Format), ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_void_p]),
-    "fldr_pack10_from_planar": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Format), ctypes.POINTER(Frame), ctypes.c_int, ctypes.c_int,
-                                               ctypes.c_void_p]),
-}
+IO, SessionConfig = yuv_structs(Format, Frame)
+_SIGNATURES = {**yuv_signatures("fldr_pack10_", Frame, IO, SessionConfig), **converter_signatures("fldr_pack10_", Format, Frame)}
 EXPORTS = tuple(_SIGNATURES)
-_lib = None
 
 
-class Pack10Error(RuntimeError):
-    def __init__(self, what, code):
-        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_pack10_error_string(code).decode(), code))
-        self.code = code
-
-
-def lib():
-    """The loaded libfldr_pack10.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (Format, Frame, IO, SessionConfig), "fldr_pack10", PACK10_VERSION)
-    return _lib
-
-
-def _check(code, what):
-    if code != 0:
-        raise Pack10Error(what, code)
+class Pack10Error(YuvError):
+    pass
 
 
 # ---- geometry ---------------------------------------------------------------------------------------------------------------------
@@ -130,8 +98,9 @@ def frame_struct(planes):
     return f
 
 
-_YUV = YuvApi(lib, "fldr_pack10_", Pack10Error, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype)
-empty_frame = _YUV.empty_frame
+_YUV = YuvApi("pack10", LIB_PATH, PACK10_VERSION, Pack10Error, _SIGNATURES, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype,
+              planar_dtype=lambda fmt: torch.uint16)
+lib, empty_frame = _YUV.lib, _YUV.empty_frame
 
 
 def luma_size(frame, fmt, W=None):
@@ -150,26 +119,13 @@ def to_planar(frames, fmt, planar=None, W=None, stream=None):
     """fldr_pack10_to_planar: a list of frames in `fmt` (tuples of one device plane tensor, pitches from their strides) -> planar BGR
     [n,3,H,W] uint16 (`planar` when given).  W: the luma width (required for v210)."""
     H, W = luma_size(frames[0], fmt, W)
-    device = frames[0][0].device
-    if planar is None:
-        planar = torch.empty(len(frames), 3, H, W, dtype=torch.uint16, device=device)
-    arr = (Frame * len(frames))(*[frame_struct(f) for f in frames])
-    _check(lib().fldr_pack10_to_planar(arr, len(frames), ctypes.byref(fmt), ctypes.c_void_p(planar.data_ptr()), int(H), int(W),
-                                       _stream_ptr(device, stream)), "fldr_pack10_to_planar")
-    return planar
+    return _YUV.to_planar(frames, fmt, H, W, planar, stream)
 
 
 def from_planar(planar, fmt, out=None, stream=None):
     """fldr_pack10_from_planar: a planar BGR device tensor [3,H,W] uint16 with contiguous rows and planes -> one frame in `fmt` (`out`: a
     tuple of one plane tensor, the pitch from its stride; allocated packed otherwise)."""
-    _, H, W = planar.shape
-    assert planar.is_contiguous() and planar.dtype == torch.uint16
-    if out is None:
-        out = empty_frame(fmt, H, W, planar.device)
-    fr = frame_struct(out)
-    _check(lib().fldr_pack10_from_planar(ctypes.c_void_p(planar.data_ptr()), ctypes.byref(fmt), ctypes.byref(fr), int(H), int(W),
-                                         _stream_ptr(planar.device, stream)), "fldr_pack10_from_planar")
-    return out
+    return _YUV.from_planar(planar, fmt, out, stream)
 
 
 class NativePack10(YuvNative):

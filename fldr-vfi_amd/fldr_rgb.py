@@ -20,8 +20,7 @@ import os
 import numpy as np
 import torch
 
-import fldr_model
-from fldr_video import YuvApi, YuvNative, YuvSession, _stream_ptr, yuv_signatures
+from fldr_video import YuvApi, YuvError, YuvNative, YuvSession, _stream_ptr, converter_signatures, yuv_signatures, yuv_structs
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libfldr_rgb.so")
@@ -57,46 +56,18 @@ class Frame(ctypes.Structure):
     _fields_ = [("plane", ctypes.c_void_p * 4), ("pitch", ctypes.c_int64 * 4)]
 
 
-class IO(ctypes.Structure):
-    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("in_", Frame * 2), ("out_format", Format),
-                ("n_t", ctypes.c_int32), ("t", ctypes.c_void_p), ("out", ctypes.POINTER(Frame))]
-
-
-class SessionConfig(ctypes.Structure):
-    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("out_format", Format), ("n_t", ctypes.c_int32),
-                ("device", ctypes.c_int32), ("t", ctypes.POINTER(ctypes.c_float)), ("reserved", ctypes.c_int32 * 4)]
-
-
+IO, SessionConfig = yuv_structs(Format, Frame)
 _SIGNATURES = {
     **yuv_signatures("fldr_rgb_", Frame, IO, SessionConfig),
-    "fldr_rgb_to_planar": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.c_int, ctypes.POINTER(Format), ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
-                                          ctypes.c_void_p]),
-    "fldr_rgb_from_planar": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Format), ctypes.POINTER(Frame), ctypes.c_int, ctypes.c_int,
-                                            ctypes.c_void_p]),
+    **converter_signatures("fldr_rgb_", Format, Frame),
     "fldr_rgb_alpha": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.POINTER(Format), ctypes.POINTER(Frame), ctypes.c_int, ctypes.POINTER(Format),
                                       ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
-_lib = None
 
 
-class RgbError(RuntimeError):
-    def __init__(self, what, code):
-        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_rgb_error_string(code).decode(), code))
-        self.code = code
-
-
-def lib():
-    """The loaded libfldr_rgb.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (Format, Frame, IO, SessionConfig), "fldr_rgb", RGB_VERSION)
-    return _lib
-
-
-def _check(code, what):
-    if code != 0:
-        raise RgbError(what, code)
+class RgbError(YuvError):
+    pass
 
 
 # ---- geometry ---------------------------------------------------------------------------------------------------------------------
@@ -142,8 +113,9 @@ def frame_struct(planes):
     return f
 
 
-_YUV = YuvApi(lib, "fldr_rgb_", RgbError, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype)
-empty_frame = _YUV.empty_frame
+_YUV = YuvApi("rgb", LIB_PATH, RGB_VERSION, RgbError, _SIGNATURES, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype,
+              planar_dtype)
+lib, empty_frame = _YUV.lib, _YUV.empty_frame
 
 
 def frame_size(frame, fmt):
@@ -157,26 +129,13 @@ def to_planar(frames, fmt, planar=None, stream=None):
     """fldr_rgb_to_planar: a list of frames in `fmt` (tuples of device plane tensors, pitches from their strides) -> planar BGR
     [n,3,H,W], uint8 or (depth 10) uint16 (`planar` when given)."""
     H, W = frame_size(frames[0], fmt)
-    device = frames[0][0].device
-    if planar is None:
-        planar = torch.empty(len(frames), 3, H, W, dtype=planar_dtype(fmt), device=device)
-    arr = (Frame * len(frames))(*[frame_struct(f) for f in frames])
-    _check(lib().fldr_rgb_to_planar(arr, len(frames), ctypes.byref(fmt), ctypes.c_void_p(planar.data_ptr()), int(H), int(W),
-                                    _stream_ptr(device, stream)), "fldr_rgb_to_planar")
-    return planar
+    return _YUV.to_planar(frames, fmt, H, W, planar, stream)
 
 
 def from_planar(planar, fmt, out=None, stream=None):
     """fldr_rgb_from_planar: a planar BGR device tensor [3,H,W] (uint8; uint16 at depth 10) with contiguous rows and planes -> one frame
     in `fmt` with opaque alpha (`out`: a tuple of plane tensors, pitches from their strides; allocated packed otherwise)."""
-    _, H, W = planar.shape
-    assert planar.is_contiguous() and planar.dtype == planar_dtype(fmt)
-    if out is None:
-        out = empty_frame(fmt, H, W, planar.device)
-    fr = frame_struct(out)
-    _check(lib().fldr_rgb_from_planar(ctypes.c_void_p(planar.data_ptr()), ctypes.byref(fmt), ctypes.byref(fr), int(H), int(W),
-                                      _stream_ptr(planar.device, stream)), "fldr_rgb_from_planar")
-    return out
+    return _YUV.from_planar(planar, fmt, out, stream)
 
 
 def alpha(frames, in_format, outs, out_format, t, stream=None):
@@ -184,10 +143,8 @@ def alpha(frames, in_format, outs, out_format, t, stream=None):
     `frames` in in_format at the times t (a float32 device tensor of len(outs) values).  -> outs."""
     H, W = frame_size(frames[0], in_format)
     assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == len(outs)
-    fin = (Frame * 2)(*[frame_struct(f) for f in frames])
-    fout = (Frame * len(outs))(*[frame_struct(f) for f in outs])
-    _check(lib().fldr_rgb_alpha(fin, ctypes.byref(in_format), fout, len(outs), ctypes.byref(out_format), ctypes.c_void_p(t.data_ptr()), int(H),
-                                int(W), _stream_ptr(t.device, stream)), "fldr_rgb_alpha")
+    _YUV.check(_YUV.fn("alpha")(_YUV.frame_array(frames), ctypes.byref(in_format), _YUV.frame_array(outs), len(outs), ctypes.byref(out_format),
+                                ctypes.c_void_p(t.data_ptr()), int(H), int(W), _stream_ptr(t.device, stream)), "alpha")
     return outs
 
 

@@ -63,18 +63,26 @@ class Frame(ctypes.Structure):
     _fields_ = [("plane", ctypes.c_void_p * 3), ("pitch", ctypes.c_int64 * 3)]
 
 
-class IO(ctypes.Structure):
-    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("in_", Frame * 2), ("out_format", Format),
-                ("n_t", ctypes.c_int32), ("t", ctypes.c_void_p), ("out", ctypes.POINTER(Frame))]
+def yuv_structs(Format, Frame):
+    """The IO and SessionConfig struct classes of a library on the model from its Format and Frame (fldr_video_io and
+    fldr_video_session_config; fldr_chroma.h, fldr_pack10.h and fldr_rgb.h lay theirs out the same)."""
+    class IO(ctypes.Structure):
+        _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("in_", Frame * 2), ("out_format", Format),
+                    ("n_t", ctypes.c_int32), ("t", ctypes.c_void_p), ("out", ctypes.POINTER(Frame))]
+
+    class SessionConfig(ctypes.Structure):
+        _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("out_format", Format), ("n_t", ctypes.c_int32),
+                    ("device", ctypes.c_int32), ("t", ctypes.POINTER(ctypes.c_float)), ("reserved", ctypes.c_int32 * 4)]
+
+    return IO, SessionConfig
 
 
-class SessionConfig(ctypes.Structure):
-    _fields_ = [("H", ctypes.c_int32), ("W", ctypes.c_int32), ("in_format", Format), ("out_format", Format), ("n_t", ctypes.c_int32),
-                ("device", ctypes.c_int32), ("t", ctypes.POINTER(ctypes.c_float)), ("reserved", ctypes.c_int32 * 4)]
+IO, SessionConfig = yuv_structs(Format, Frame)
 
 
 def yuv_signatures(prefix, Frame, IO, SessionConfig):
-    """The functions every YUV library on the model exports (fldr_video.h, fldr_chroma.h), as fldr_model.load_library takes them."""
+    """The functions every library on the model exports (fldr_video.h, fldr_chroma.h, fldr_pack10.h, fldr_rgb.h), as
+    fldr_model.load_library takes them."""
     return {
         prefix + "version": (ctypes.c_int, []),
         prefix + "error_string": (ctypes.c_char_p, [ctypes.c_int]),
@@ -88,9 +96,18 @@ def yuv_signatures(prefix, Frame, IO, SessionConfig):
     }
 
 
+def converter_signatures(prefix, Format, Frame):
+    """The two converters alone, which the chroma, pack10 and rgb libraries export beside the functions of yuv_signatures."""
+    return {
+        prefix + "to_planar": (ctypes.c_int, [ctypes.POINTER(Frame), ctypes.c_int, ctypes.POINTER(Format), ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
+                                              ctypes.c_void_p]),
+        prefix + "from_planar": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(Format), ctypes.POINTER(Frame), ctypes.c_int, ctypes.c_int,
+                                                ctypes.c_void_p]),
+    }
+
+
 _SIGNATURES = yuv_signatures("fldr_video_", Frame, IO, SessionConfig)
 EXPORTS = tuple(_SIGNATURES)
-_lib = None
 # libfldr_video_test.so (-DFLDR_TEST_HOOKS): the same sources + the converter hooks of include/fldr_video_test_hooks.h; tests only
 TEST_LIB_PATH = os.path.join(_HERE, "libfldr_video_test.so")
 _HOOK_SIGNATURES = {
@@ -102,23 +119,17 @@ HOOKS = tuple(_HOOK_SIGNATURES)
 _hooks_lib = None
 
 
-class VideoError(RuntimeError):
-    def __init__(self, what, code):
-        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_video_error_string(code).decode(), code))
+class YuvError(RuntimeError):
+    """A failed call `what` of a library on the model: its code and the library's string for it (YuvApi.failure makes one); each module
+    derives its own class."""
+
+    def __init__(self, what, code, text):
+        super().__init__("%s failed: %s (code %d)" % (what, text, code))
         self.code = code
 
 
-def lib():
-    """The loaded libfldr_video.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
-    global _lib
-    if _lib is None:
-        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (Format, Frame, IO, SessionConfig), "fldr_video", VIDEO_VERSION)
-    return _lib
-
-
-def _check(code, what):
-    if code != 0:
-        raise VideoError(what, code)
+class VideoError(YuvError):
+    pass
 
 
 def test_hooks():
@@ -183,8 +194,8 @@ def debug_to_planar(frames, fmt, pair=None, stream=None):
     if pair is None:
         pair = torch.empty(2, 3, H, W, dtype=plane_dtype(fmt), device=frames[0][0].device)
     arr = (Frame * 2)(*[frame_struct(f) for f in frames])
-    _check(test_hooks().fldr_video_debug_to_planar(arr, ctypes.byref(fmt), ctypes.c_void_p(pair.data_ptr()), int(H), int(W),
-                                                   _stream_ptr(pair.device, stream)), "fldr_video_debug_to_planar")
+    _YUV.check(test_hooks().fldr_video_debug_to_planar(arr, ctypes.byref(fmt), ctypes.c_void_p(pair.data_ptr()), int(H), int(W),
+                                                       _stream_ptr(pair.device, stream)), "debug_to_planar")
     return pair
 
 
@@ -196,8 +207,8 @@ def debug_from_planar(planar, fmt, out=None, stream=None):
     if out is None:
         out = empty_frame(fmt, H, W, planar.device)
     fr = frame_struct(out)
-    _check(test_hooks().fldr_video_debug_from_planar(ctypes.c_void_p(planar.data_ptr()), ctypes.byref(fr), ctypes.byref(fmt), int(H), int(W),
-                                                     _stream_ptr(planar.device, stream)), "fldr_video_debug_from_planar")
+    _YUV.check(test_hooks().fldr_video_debug_from_planar(ctypes.c_void_p(planar.data_ptr()), ctypes.byref(fr), ctypes.byref(fmt), int(H), int(W),
+                                                         _stream_ptr(planar.device, stream)), "debug_from_planar")
     return out
 
 
@@ -207,20 +218,35 @@ def debug_last_path():
 
 
 class YuvApi:
-    """One YUV library on the model, as YuvNative and YuvSession use it: its handle (`lib`, a function), the `fldr_<name>_` prefix of its
-    functions, its error class, its struct classes and the geometry functions of its frames."""
+    """One library on the model, as YuvNative and YuvSession use it: its name (the functions are fldr_<name>_*), path and header version,
+    its error class, the signatures of its functions, its struct classes and the geometry functions of its frames (planar_dtype: the
+    sample type of the model's planar BGR frames for a format, where that is not the planes').  Loads the library on first use."""
 
-    def __init__(self, lib, prefix, error, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype):
-        self.lib, self.prefix, self.error = lib, prefix, error
+    def __init__(self, name, path, version, error, signatures, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype,
+                 planar_dtype=None):
+        self.name, self.prefix, self.path, self.version, self.error, self.signatures = name, "fldr_%s_" % name, path, version, error, signatures
         self.Format, self.Frame, self.IO, self.SessionConfig = Format, Frame, IO, SessionConfig
         self.frame_struct, self.plane_shapes, self.plane_dtype = frame_struct, plane_shapes, plane_dtype
+        self.planar_dtype = planar_dtype or plane_dtype
+        self._lib = None
+
+    def lib(self):
+        """The loaded library, checked against this binding (struct sizes, header version); raises when it has not been built."""
+        if self._lib is None:
+            self._lib = fldr_model.load_library(self.path, self.signatures, (self.Format, self.Frame, self.IO, self.SessionConfig),
+                                                "fldr_" + self.name, self.version)
+        return self._lib
 
     def fn(self, name):
         return getattr(self.lib(), self.prefix + name)
 
+    def failure(self, name, code):
+        """The library's error for the code its function `name` returned."""
+        return self.error(self.prefix + name, code, self.fn("error_string")(code).decode())
+
     def check(self, code, name):
         if code != 0:
-            raise self.error(self.prefix + name, code)
+            raise self.failure(name, code)
 
     def empty_frame(self, fmt, H, W, device):
         return tuple(torch.empty(r, c, dtype=self.plane_dtype(fmt), device=device) for r, c in self.plane_shapes(fmt, H, W))
@@ -228,8 +254,32 @@ class YuvApi:
     def frame_array(self, frames):
         return (self.Frame * len(frames))(*[self.frame_struct(f) for f in frames])
 
+    # the converters alone (they need no model; libfldr_video.so exports none)
+    def to_planar(self, frames, fmt, H, W, planar=None, stream=None):
+        """fldr_<name>_to_planar: a list of H x W frames in `fmt` (tuples of device plane tensors, pitches from their strides) -> planar
+        BGR [n,3,H,W] (`planar` when given)."""
+        device = frames[0][0].device
+        if planar is None:
+            planar = torch.empty(len(frames), 3, H, W, dtype=self.planar_dtype(fmt), device=device)
+        self.check(self.fn("to_planar")(self.frame_array(frames), len(frames), ctypes.byref(fmt), ctypes.c_void_p(planar.data_ptr()), int(H), int(W),
+                                        _stream_ptr(device, stream)), "to_planar")
+        return planar
 
-_YUV = YuvApi(lib, "fldr_video_", VideoError, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype)
+    def from_planar(self, planar, fmt, out=None, stream=None):
+        """fldr_<name>_from_planar: a planar BGR device tensor [3,H,W] with contiguous rows and planes -> one frame in `fmt` (`out`: a
+        tuple of plane tensors, pitches from their strides; allocated packed otherwise)."""
+        _, H, W = planar.shape
+        assert planar.is_contiguous() and planar.dtype == self.planar_dtype(fmt)
+        if out is None:
+            out = self.empty_frame(fmt, H, W, planar.device)
+        fr = self.frame_struct(out)
+        self.check(self.fn("from_planar")(ctypes.c_void_p(planar.data_ptr()), ctypes.byref(fmt), ctypes.byref(fr), int(H), int(W),
+                                          _stream_ptr(planar.device, stream)), "from_planar")
+        return out
+
+
+_YUV = YuvApi("video", LIB_PATH, VIDEO_VERSION, VideoError, _SIGNATURES, Format, Frame, IO, SessionConfig, frame_struct, plane_shapes, plane_dtype)
+lib = _YUV.lib
 
 
 class YuvNative:
@@ -244,7 +294,7 @@ class YuvNative:
     def workspace_bytes(self, H, W, n_t=1):
         n = self._yuv.fn("workspace_bytes")(self.model._h, int(H), int(W), int(n_t))
         if n < 0:
-            raise self._yuv.error(self._yuv.prefix + "workspace_bytes", int(n))
+            raise self._yuv.failure("workspace_bytes", int(n))
         return int(n)
 
     def workspace(self, H, W, n_t=1):

@@ -28,7 +28,8 @@ namespace fldr_pack10_impl {
 #define PK_TX 64                 // threads along a row
 #define PK_TY 4                  // rows per block
 
-using namespace fldr_yuv_run;                      // Smp, ld_wide / st_wide, load_run / store_run, pack2h
+using namespace fldr_yuv_run;                      // Smp, ld_wide / st_wide, load_run / store_run, load_words / store_words, pack2h;
+                                                   // al, row_grid, YUV_LAUNCH_VEC, launched
 
 typedef uint16_t T;                                // a planar BGR sample
 constexpr int MID = Smp<T>::MID, MAXV = Smp<T>::MAXV;
@@ -129,8 +130,8 @@ __global__ __launch_bounds__(PK_TX * PK_TY) void pack10_to_planar_kernel(InArgs 
     } else {
         uint32_t w[R];
         if (VEC) {
-            ld_wide<4 * R>(row0 + (int64_t)x0 * 4, w);
-        } else {
+            load_words<R, true>(row0, x0, W, w);
+        } else {                                     // in the kernel: DESIGN_LOG.md ("Chroma, pack10 and rgb", device code)
 #pragma unroll
             for (int j = 0; j < R; ++j) w[j] = reinterpret_cast<const uint32_t*>(row0)[min(x0 + j, W - 1)];
         }
@@ -244,8 +245,8 @@ __global__ __launch_bounds__(PK_TX * PK_TY) void pack10_from_planar_kernel(OutAr
 #pragma unroll
         for (int j = 0; j < R; ++j) w[j] = word3(uo[j], yb[j], vo[j]) | 0xc0000000u;            // alpha = 3
         if (VEC) {
-            st_wide<4 * R>(row0 + (int64_t)x0 * 4, w);
-        } else {
+            store_words<R, true>(row0, x0, W, w);
+        } else {                                     // in the kernel, like the input kernel's loads
 #pragma unroll
             for (int j = 0; j < R; ++j)
                 if (x0 + j < W) reinterpret_cast<uint32_t*>(row0)[x0 + j] = w[j];
@@ -254,8 +255,6 @@ __global__ __launch_bounds__(PK_TX * PK_TY) void pack10_from_planar_kernel(OutAr
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
-static bool al(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-static dim3 grid_of(int R, int H, int W, int n) { return dim3(((W + R - 1) / R + PK_TX - 1) / PK_TX, (H + PK_TY - 1) / PK_TY, n); }
 // what the wide form asks of the planar BGR side: v210 moves 12 bytes per lane (a 4-byte aligned start of every row), the others 16
 static bool planar_wide(const fldr_pack10_format& fmt, const void* planar, int W) {
     return fmt.container == FLDR_PACK10_V210 ? W % 2 == 0 && al(planar, 4) : W % 8 == 0 && al(planar, 16);
@@ -275,35 +274,25 @@ int to_planar(const fldr_pack10_frame* in, int n, const fldr_pack10_format& fmt,
     for (int f = 0; f < MAX_FRAMES; ++f) {
         a.plane[f] = f < n ? (const uint8_t*)in[f].plane[0] : nullptr;
         a.pitch[f] = f < n ? in[f].pitch[0] : 0;
-        if (f < n) vec = vec && al(in[f].plane[0], 16) && (in[f].pitch[0] & 15) == 0;
+        if (f < n) vec = vec && al(in[f].plane[0], 16) && al(in[f].pitch[0], 16);
     }
     a.dst = (uint8_t*)planar; a.H = H; a.W = W; a.k = k;
     const dim3 block(PK_TX, PK_TY);
-#define GO(C)                                                                                                            \
-    do {                                                                                                                 \
-        if (vec) hipLaunchKernelGGL((pack10_to_planar_kernel<C, true>), grid_of(RUN<C>, H, W, n), block, 0, stream, a);  \
-        else hipLaunchKernelGGL((pack10_to_planar_kernel<C, false>), grid_of(RUN<C>, H, W, n), block, 0, stream, a);     \
-    } while (0)
+#define GO(C) YUV_LAUNCH_VEC(pack10_to_planar_kernel, vec, (row_grid<PK_TX, PK_TY>(RUN<C>, H, W, n)), block, stream, a, C)
     PK_DISPATCH(fmt);
 #undef GO
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launched();
 }
 
 int from_planar(const void* planar, const fldr_pack10_frame& out, const fldr_pack10_format& fmt, const YuvCoeffs& k, int H, int W, hipStream_t stream) {
     OutArgs a;
-    const bool vec = planar_wide(fmt, planar, W) && al(out.plane[0], 16) && (out.pitch[0] & 15) == 0;
+    const bool vec = planar_wide(fmt, planar, W) && al(out.plane[0], 16) && al(out.pitch[0], 16);
     a.src = (const uint8_t*)planar; a.plane = (uint8_t*)out.plane[0]; a.pitch = out.pitch[0]; a.H = H; a.W = W; a.k = k;
     const dim3 block(PK_TX, PK_TY);
-#define GO(C)                                                                                                              \
-    do {                                                                                                                   \
-        if (vec) hipLaunchKernelGGL((pack10_from_planar_kernel<C, true>), grid_of(RUN<C>, H, W, 1), block, 0, stream, a);  \
-        else hipLaunchKernelGGL((pack10_from_planar_kernel<C, false>), grid_of(RUN<C>, H, W, 1), block, 0, stream, a);     \
-    } while (0)
+#define GO(C) YUV_LAUNCH_VEC(pack10_from_planar_kernel, vec, (row_grid<PK_TX, PK_TY>(RUN<C>, H, W, 1)), block, stream, a, C)
     PK_DISPATCH(fmt);
 #undef GO
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launched();
 }
 
 }  // namespace fldr_pack10_impl

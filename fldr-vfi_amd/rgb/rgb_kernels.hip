@@ -34,7 +34,8 @@ namespace fldr_rgb_impl {
 #define RG_ALPHA_THREADS 256     // threads of an alpha block (one row at a time)
 #define RG_ALPHA_BLOCKS 2048     // row walkers at most
 
-using namespace fldr_yuv_run;                      // Smp, ld_wide / st_wide, load_run / store_run, pack2h, pack4, unpack
+using namespace fldr_yuv_run;                      // Smp, ld_wide / st_wide, load_run / store_run, load_words / store_words, pack2h, pack4, unpack;
+                                                   // al, row_grid, YUV_LAUNCH_VEC, launched
 
 // Where the channels sit in a pixel word (bit offsets), the bits of a colour field and the planar sample type.
 template <int L> struct Lay;
@@ -75,8 +76,8 @@ __global__ __launch_bounds__(RG_TX * RG_TY) void rgb_words_to_planar_kernel(InAr
     const uint8_t* row0 = a.plane[f] + (int64_t)y * a.pitch[f];
     uint32_t w[R];
     if (VEC) {
-        ld_wide<4 * R>(row0 + (int64_t)x0 * 4, w);
-    } else {
+        load_words<R, true>(row0, x0, W, w);
+    } else {                                         // in the kernel: DESIGN_LOG.md ("Chroma, pack10 and rgb", device code)
 #pragma unroll
         for (int j = 0; j < R; ++j) w[j] = reinterpret_cast<const uint32_t*>(row0)[min(x0 + j, W - 1)];
     }
@@ -121,8 +122,8 @@ __global__ __launch_bounds__(RG_TX * RG_TY) void rgb_words_from_planar_kernel(Ou
     for (int j = 0; j < R; ++j) w[j] = pixel_word<L>(px[0][j] & M, px[1][j] & M, px[2][j] & M);
     uint8_t* row0 = a.plane + (int64_t)y * a.pitch;
     if (VEC) {
-        st_wide<4 * R>(row0 + (int64_t)x0 * 4, w);
-    } else {
+        store_words<R, true>(row0, x0, W, w);
+    } else {                                         // in the kernel, like the input kernel's loads
 #pragma unroll
         for (int j = 0; j < R; ++j)
             if (x0 + j < W) reinterpret_cast<uint32_t*>(row0)[x0 + j] = w[j];
@@ -187,12 +188,7 @@ struct AlphaArgs {
 template <int K, bool VEC> __device__ __forceinline__ void load_alpha(const uint8_t* row, int x, int W, int shift, uint32_t mask, uint32_t* al) {
     if constexpr (K == AK_WORD) {
         uint32_t w[4];
-        if (VEC) {
-            ld_wide<16>(row + (int64_t)x * 4, w);
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) w[j] = reinterpret_cast<const uint32_t*>(row)[min(x + j, W - 1)];
-        }
+        load_words<4, VEC>(row, x, W, w);
 #pragma unroll
         for (int j = 0; j < 4; ++j) al[j] = (w[j] >> shift) & mask;
     } else {
@@ -258,13 +254,6 @@ __global__ __launch_bounds__(RG_ALPHA_THREADS) void rgb_alpha_kernel(AlphaArgs a
 }
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
-static bool al(const void* p, uintptr_t n) { return ((uintptr_t)p & (n - 1)) == 0; }
-static bool al(int64_t v, int64_t n) { return (v & (n - 1)) == 0; }
-static dim3 grid_of(int run, int H, int W, int n) { return dim3(((W + run - 1) / run + RG_TX - 1) / RG_TX, (H + RG_TY - 1) / RG_TY, n); }
-static int launched() {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
-}
 
 // Call GO(L) for the word layout of `fmt` (the caller checked the format).
 #define RG_DISPATCH(fmt)                                                     \
@@ -284,14 +273,9 @@ static const int GBR_OF[3] = {1, 0, 2};
 
 static int launch_planes(const PlaneArgs& a, bool wide16, bool vec, int H, int W, int n, hipStream_t stream) {
     const dim3 block(RG_TX, RG_TY);
-    const dim3 grid = grid_of(RUN_PLANE_BYTES / (wide16 ? 2 : 1), H, W, n);
-    if (wide16) {
-        if (vec) hipLaunchKernelGGL((rgb_planes_kernel<uint16_t, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((rgb_planes_kernel<uint16_t, false>), grid, block, 0, stream, a);
-    } else {
-        if (vec) hipLaunchKernelGGL((rgb_planes_kernel<uint8_t, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((rgb_planes_kernel<uint8_t, false>), grid, block, 0, stream, a);
-    }
+    const dim3 grid = row_grid<RG_TX, RG_TY>(RUN_PLANE_BYTES / (wide16 ? 2 : 1), H, W, n);
+    if (wide16) YUV_LAUNCH_VEC(rgb_planes_kernel, vec, grid, block, stream, a, uint16_t);
+    else YUV_LAUNCH_VEC(rgb_planes_kernel, vec, grid, block, stream, a, uint8_t);
     return launched();
 }
 
@@ -320,11 +304,7 @@ int to_planar(const fldr_rgb_frame* in, int n, const fldr_rgb_format& fmt, void*
         if (f < n) vec = vec && al(in[f].plane[0], 16) && al(in[f].pitch[0], 16);
     }
     a.dst = (uint8_t*)planar; a.H = H; a.W = W;
-#define GO(L)                                                                                                                 \
-    do {                                                                                                                      \
-        if (vec) hipLaunchKernelGGL((rgb_words_to_planar_kernel<L, true>), grid_of(RUN_WORDS, H, W, n), block, 0, stream, a);  \
-        else hipLaunchKernelGGL((rgb_words_to_planar_kernel<L, false>), grid_of(RUN_WORDS, H, W, n), block, 0, stream, a);     \
-    } while (0)
+#define GO(L) YUV_LAUNCH_VEC(rgb_words_to_planar_kernel, vec, (row_grid<RG_TX, RG_TY>(RUN_WORDS, H, W, n)), block, stream, a, L)
     RG_DISPATCH(fmt);
 #undef GO
     return launched();
@@ -352,11 +332,7 @@ int from_planar(const void* planar, const fldr_rgb_frame& out, const fldr_rgb_fo
     OutArgs a;
     const bool vec = W % RUN_WORDS == 0 && al(planar, (uintptr_t)(RUN_WORDS * sb)) && al(out.plane[0], 16) && al(out.pitch[0], 16);
     a.src = (const uint8_t*)planar; a.plane = (uint8_t*)out.plane[0]; a.pitch = out.pitch[0]; a.H = H; a.W = W;
-#define GO(L)                                                                                                                   \
-    do {                                                                                                                        \
-        if (vec) hipLaunchKernelGGL((rgb_words_from_planar_kernel<L, true>), grid_of(RUN_WORDS, H, W, 1), block, 0, stream, a);  \
-        else hipLaunchKernelGGL((rgb_words_from_planar_kernel<L, false>), grid_of(RUN_WORDS, H, W, 1), block, 0, stream, a);     \
-    } while (0)
+#define GO(L) YUV_LAUNCH_VEC(rgb_words_from_planar_kernel, vec, (row_grid<RG_TX, RG_TY>(RUN_WORDS, H, W, 1)), block, stream, a, L)
     RG_DISPATCH(fmt);
 #undef GO
     return launched();
@@ -378,22 +354,18 @@ int write_alpha(const fldr_rgb_frame in[2], const fldr_rgb_format& fin, const fl
     bool vec = W % 4 == 0;
     for (int f = 0; f < 2; ++f) {
         a.in[f] = (const uint8_t*)in[f].plane[pi.plane]; a.in_pitch[f] = in[f].pitch[pi.plane];
-        vec = vec && al(a.in[f], pi.unit) && al(a.in_pitch[f], (int64_t)pi.unit);
+        vec = vec && al(a.in[f], pi.unit) && al(a.in_pitch[f], pi.unit);
     }
     for (int k = 0; k < n; ++k) {
         a.out[k] = (uint8_t*)out[k].plane[po.plane]; a.out_pitch[k] = out[k].pitch[po.plane];
-        vec = vec && al(a.out[k], po.unit) && al(a.out_pitch[k], (int64_t)po.unit);
+        vec = vec && al(a.out[k], po.unit) && al(a.out_pitch[k], po.unit);
     }
     a.t = t; a.H = H; a.W = W;
     a.blend = fout.alpha == FLDR_RGB_ALPHA_BLEND;
     a.in_shift = pi.shift; a.out_shift = po.shift;
     a.mask = (1u << alpha_bits(fout)) - 1u;
     const dim3 grid((unsigned)(H < RG_ALPHA_BLOCKS ? H : RG_ALPHA_BLOCKS), (unsigned)n);
-#define GO(SK, DK)                                                                                                   \
-    do {                                                                                                             \
-        if (vec) hipLaunchKernelGGL((rgb_alpha_kernel<SK, DK, true>), grid, dim3(RG_ALPHA_THREADS), 0, stream, a);   \
-        else hipLaunchKernelGGL((rgb_alpha_kernel<SK, DK, false>), grid, dim3(RG_ALPHA_THREADS), 0, stream, a);      \
-    } while (0)
+#define GO(SK, DK) YUV_LAUNCH_VEC(rgb_alpha_kernel, vec, grid, dim3(RG_ALPHA_THREADS), stream, a, SK, DK)
     // alpha of one width on both sides (the caller checked): a 16-bit plane only meets a 16-bit plane
     if (pi.kind == AK_U16) GO(AK_U16, AK_U16);
     else if (pi.kind == AK_WORD && po.kind == AK_WORD) GO(AK_WORD, AK_WORD);

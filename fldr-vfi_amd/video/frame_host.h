@@ -1,9 +1,10 @@
 // The host side of the frame contract of include/fldr_video.h (what a valid format and a valid frame are, how large a plane is) and the
 // plumbing of a stream object (fldr_video_session, fldr_rate): a device, a stream, one device block, one pinned block, packed frames in
-// them.  Included by video_host.hip and ../chroma/chroma_host.hip (through yuv_stream_host.h), by the shutter and light libraries' host
-// files and, through ../rate/rate_plan.h, by the rate, pipe and cadence libraries': each refuses exactly the frames libfldr_video.so
-// refuses because all compile this text (the chroma library with its own FrameRules, below).  Everything is in the unnamed namespace:
-// nothing here becomes a symbol of any library.
+// them.  Included by video_host.hip, ../chroma/chroma_host.hip, ../pack10/pack10_host.hip and ../rgb/rgb_host.hip (through
+// yuv_stream_host.h), by the shutter and light libraries' host files and, through ../rate/rate_plan.h, by the rate, pipe, cadence, field
+// and pulldown libraries': each refuses exactly the frames libfldr_video.so refuses because all compile this text (the chroma, pack10
+// and rgb libraries with their own FrameRules, below).  Everything is in the unnamed namespace: nothing here becomes a symbol of any
+// library.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -39,9 +40,11 @@ int64_t row_bytes(const fldr_video_format& f, int p, int W) {
 
 int rows_of(int p, int H) { return p == 0 ? H : (H + 1) / 2; }
 
-// The functions below are written once for every YUV format struct (a `depth` word: 10 = 16-bit samples, and frames of plane[3] /
-// pitch[3]).  A library states its own rules in a FrameRules<Format>: the frame type, its E_PLANE / E_PITCH codes, the planes of a
-// format, the bytes per row and the rows of plane p.  These are fldr_video.h's (4:2:0); ../chroma/chroma_host.hip has the other.
+// The functions below are written once for every format struct (a `depth` word: 10 = 16-bit samples, and frames of plane[] / pitch[]).
+// A library states its own rules in a FrameRules<Format>, specialised before the first call that uses it: the frame type, its E_PLANE /
+// E_PITCH codes, the planes of a format, the bytes per row and the rows of plane p, and the format's address unit (the bytes of which
+// every plane pointer and pitch must be a multiple beyond the sample size: 4 for a container of 32-bit words, 0 for none).  These are
+// fldr_video.h's (4:2:0); the chroma, pack10 and rgb libraries' host files have theirs.
 template <class Format> struct FrameRules;
 template <> struct FrameRules<fldr_video_format> {
     using Frame = fldr_video_frame;
@@ -49,15 +52,24 @@ template <> struct FrameRules<fldr_video_format> {
     static int planes(const fldr_video_format& f) { return planes_of(f.layout); }
     static int64_t row_bytes(const fldr_video_format& f, int p, int W) { return ::row_bytes(f, p, W); }
     static int rows(const fldr_video_format&, int p, int H) { return rows_of(p, H); }
+    static int unit(const fldr_video_format&) { return 0; }
 };
 template <class Format> using FrameOf = typename FrameRules<Format>::Frame;
 
+// Every plane and every pitch by the sample size first, then every plane and every pitch by the address unit: a frame with two faults
+// gets the code of the earlier of these four passes.
 template <class Format> int check_frame(const FrameOf<Format>& fr, const Format& f, int W) {
     using R = FrameRules<Format>;
     const bool words = f.depth == 10;
-    for (int p = 0; p < R::planes(f); ++p) if (!fr.plane[p] || (words && ((uintptr_t)fr.plane[p] & 1))) return R::E_PLANE;
-    for (int p = 0; p < R::planes(f); ++p)
+    const int np = R::planes(f);
+    for (int p = 0; p < np; ++p) if (!fr.plane[p] || (words && ((uintptr_t)fr.plane[p] & 1))) return R::E_PLANE;
+    for (int p = 0; p < np; ++p)
         if (fr.pitch[p] < R::row_bytes(f, p, W) || (words && (fr.pitch[p] & 1))) return R::E_PITCH;
+    const uintptr_t unit = (uintptr_t)R::unit(f);
+    if (unit) {
+        for (int p = 0; p < np; ++p) if ((uintptr_t)fr.plane[p] % unit) return R::E_PLANE;
+        for (int p = 0; p < np; ++p) if ((uintptr_t)fr.pitch[p] % unit) return R::E_PITCH;
+    }
     return 0;
 }
 

@@ -12,14 +12,14 @@ namespace {
 
 const YuvCoeffs& coeffs(const fldr_video_format& f) { return deep(f) ? YUV_COEFFS_10[f.matrix][f.range] : YUV_COEFFS[f.matrix][f.range]; }
 
-struct VideoLib {
+struct VideoLib : LibDefaults {
     using Format = fldr_video_format;
     using Frame = fldr_video_frame;
     using Io = fldr_video_io;
     using Config = fldr_video_session_config;
     static constexpr int E_ARG = FLDR_VIDEO_E_ARG, E_FORMAT = FLDR_VIDEO_E_FORMAT, E_WORKSPACE = FLDR_VIDEO_E_WORKSPACE, E_DEVICE = FLDR_VIDEO_E_DEVICE;
     static int check_format(const Format& f) { return ::check_format(f); }
-    static int to_planar(const Frame in[2], const Format& f, void* pair, int H, int W, hipStream_t s) {
+    static int to_planar(const Frame* in, int, const Format& f, void* pair, int H, int W, hipStream_t s) {      // always the pair
         return yuv420_to_planar_pair(in, f, coeffs(f), pair, H, W, s);
     }
     static int from_planar(const void* planar, const Frame& out, const Format& f, int H, int W, hipStream_t s) {
@@ -42,20 +42,11 @@ extern "C" FLDR_VIDEO_API const char* fldr_video_error_string(int code) {
     case FLDR_VIDEO_E_PLANE: return "fldr_video: null plane pointer (or an odd address at depth 10)";
     case FLDR_VIDEO_E_WORKSPACE: return "fldr_video: workspace missing, misaligned or too small";
     case FLDR_VIDEO_E_DEVICE: return "fldr_video: no such device or out of memory";
-    default: return code > -100 && code < 0 ? fldr_model_error_string(code) : code > 0 ? hipGetErrorString((hipError_t)code)
-                                                                                      : "fldr_video: unknown error";
+    default: return passed_error_string(code, "fldr_video: unknown error");
     }
 }
 
-extern "C" FLDR_VIDEO_API int fldr_video_sizeof(int which) {
-    switch (which) {
-    case 0: return (int)sizeof(fldr_video_format);
-    case 1: return (int)sizeof(fldr_video_frame);
-    case 2: return (int)sizeof(fldr_video_io);
-    case 3: return (int)sizeof(fldr_video_session_config);
-    default: return FLDR_VIDEO_E_ARG;
-    }
-}
+extern "C" FLDR_VIDEO_API int fldr_video_sizeof(int which) { return struct_sizeof<VideoLib>(which); }
 
 extern "C" FLDR_VIDEO_API int64_t fldr_video_workspace_bytes(const fldr_model* m, int H, int W, int n_t) { return workspace_bytes<VideoLib>(m, H, W, n_t); }
 
@@ -85,7 +76,7 @@ extern "C" FLDR_VIDEO_API int fldr_video_debug_to_planar(const fldr_video_frame 
     if (!in || !format || !pair || ((uintptr_t)pair & (ALIGN - 1)) || H < 2 || W < 2) return FLDR_VIDEO_E_ARG;
     CK(check_format(*format));
     for (int f = 0; f < 2; ++f) CK(check_frame(in[f], *format, W));
-    return VideoLib::to_planar(in, *format, pair, H, W, (hipStream_t)stream);
+    return VideoLib::to_planar(in, 2, *format, pair, H, W, (hipStream_t)stream);
 }
 
 extern "C" FLDR_VIDEO_API int fldr_video_debug_from_planar(const void* planar, const fldr_video_frame* out_frame, const fldr_video_format* format,

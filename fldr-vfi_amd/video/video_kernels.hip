@@ -181,20 +181,15 @@ __global__ __launch_bounds__(VK_TX * VK_TY) void planar_to_yuv420_kernel(OutArgs
 
 // ---- launchers -----------------------------------------------------------------------------------------------------------------
 // KERNEL<T, layout, vec><<<grid, block, 0, stream>>>(a)
-#define VK_LAUNCH(KERNEL, T, layout, vec, grid, block, stream, a)                                                       \
-    do {                                                                                                                \
-        if ((layout) == FLDR_VIDEO_NV12) {                                                                              \
-            if (vec) hipLaunchKernelGGL((KERNEL<T, FLDR_VIDEO_NV12, true>), grid, block, 0, stream, a);                 \
-            else hipLaunchKernelGGL((KERNEL<T, FLDR_VIDEO_NV12, false>), grid, block, 0, stream, a);                    \
-        } else {                                                                                                        \
-            if (vec) hipLaunchKernelGGL((KERNEL<T, FLDR_VIDEO_I420, true>), grid, block, 0, stream, a);                 \
-            else hipLaunchKernelGGL((KERNEL<T, FLDR_VIDEO_I420, false>), grid, block, 0, stream, a);                    \
-        }                                                                                                               \
+#define VK_LAUNCH(KERNEL, T, layout, vec, grid, block, stream, a)                                          \
+    do {                                                                                                   \
+        if ((layout) == FLDR_VIDEO_NV12) YUV_LAUNCH_VEC(KERNEL, vec, grid, block, stream, a, T, FLDR_VIDEO_NV12); \
+        else YUV_LAUNCH_VEC(KERNEL, vec, grid, block, stream, a, T, FLDR_VIDEO_I420);                      \
     } while (0)
 
 // VEC needs every pointer and pitch aligned to a lane's 4 samples.  That includes the planar buffer: every caller passes one aligned to
 // the workspace alignment (the offsets of the forward's plan; the debug hooks refuse anything else), so testing it changes no path.
-template <typename T> static bool al_run(const void* p, int64_t pitch = 0) { return (((uintptr_t)p | (uintptr_t)pitch) & (4 * sizeof(T) - 1)) == 0; }
+template <typename T> static bool al_run(const void* p, int64_t pitch = 0) { return al(p, 4 * sizeof(T)) && al(pitch, 4 * sizeof(T)); }
 
 // -> the launch's error; vec: the form chosen
 template <typename T>
@@ -209,10 +204,9 @@ static int to_planar_t(const fldr_video_frame in[2], int layout, const YuvCoeffs
             if (p < np) vec = vec && al_run<T>(in[f].plane[p], in[f].pitch[p]);
         }
     a.dst = (uint8_t*)pair; a.H = H; a.W = W; a.k = k;
-    const dim3 grid((((W + 3) >> 2) + VK_TX - 1) / VK_TX, (H + VK_TY - 1) / VK_TY, 2), block(VK_TX, VK_TY);
+    const dim3 grid = row_grid<VK_TX, VK_TY>(4, H, W, 2), block(VK_TX, VK_TY);
     VK_LAUNCH(yuv420_to_planar_pair_kernel, T, layout, vec, grid, block, stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launched();
 }
 
 template <typename T>
@@ -227,10 +221,9 @@ static int from_planar_t(const void* planar, const fldr_video_frame& out, int la
     }
     a.src = (const uint8_t*)planar; a.H = H; a.W = W; a.k = k;
     const int ch = (H + 1) >> 1;
-    const dim3 grid((((W + 3) >> 2) + VK_TX - 1) / VK_TX, (ch + VK_TY - 1) / VK_TY, 1), block(VK_TX, VK_TY);
+    const dim3 grid = row_grid<VK_TX, VK_TY>(4, ch, W, 1), block(VK_TX, VK_TY);
     VK_LAUNCH(planar_to_yuv420_kernel, T, layout, vec, grid, block, stream, a);
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : (int)e;
+    return launched();
 }
 
 int yuv420_to_planar_pair(const fldr_video_frame in[2], const fldr_video_format& fmt, const YuvCoeffs& k, void* pair, int H, int W, hipStream_t stream) {

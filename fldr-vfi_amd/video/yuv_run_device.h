@@ -1,8 +1,11 @@
 // Runs of YUV / BGR samples along a row, device side, inlined into each converter kernel that uses them: the constants of a sample type
 // (Smp), values packed into dwords (pack2b, pack2h, pack4) and taken out of them (unpack), one wide access per lane (ld_wide, st_wide), a
-// run of sample groups read or written either that way or sample by sample (load_run, store_run), and a 16-bit container word <-> its
-// 10-bit code value (dec, enc).  Included by video_kernels.hip (4:2:0; ../light compiles that file again) and
-// ../chroma/chroma_kernels.hip (4:2:2, 4:4:4).  Which samples a lane owns, the taps and the colour arithmetic stay with the including
+// run of sample groups read or written either that way or sample by sample (load_run, store_run), the same for a row of one dword per
+// pixel (load_words, store_words), and a 16-bit container word <-> its 10-bit code value (dec, enc).  Then, host side, how such a
+// kernel is launched: the alignment predicate of the wide form (al), the grid of a kernel whose threads own runs along rows (row_grid),
+// the launch of the VEC or the !VEC instance (YUV_LAUNCH_VEC) and its error as a code (launched).  Included by video_kernels.hip
+// (4:2:0; ../light compiles that file again), ../chroma/chroma_kernels.hip (4:2:2, 4:4:4), ../pack10/pack10_kernels.hip (v210, Y210,
+// Y410) and ../rgb/rgb_kernels.hip (RGB, alpha).  Which samples a lane owns, the taps and the colour arithmetic stay with the including
 // kernel.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -109,11 +112,58 @@ __device__ __forceinline__ void store_run(uint8_t* row, int g0, int lim, const i
     }
 }
 
+// N pixel dwords (one per pixel: Y410, the RGB word layouts) from pixel x0 of `row`: w[N].  !VEC: pixel indices clamped to lim - 1.
+// The four word kernels of ../pack10 and ../rgb call the VEC forms only and keep their per-sample loops in the kernel: written through
+// these helpers, hipcc gave those kernels other code than before (DESIGN_LOG.md); the alpha kernels take both forms from here.
+template <int N, bool VEC>
+__device__ __forceinline__ void load_words(const uint8_t* row, int x0, int lim, uint32_t* w) {
+    if (VEC) {
+        ld_wide<4 * N>(row + (int64_t)x0 * 4, w);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j) w[j] = reinterpret_cast<const uint32_t*>(row)[min(x0 + j, lim - 1)];
+    }
+}
+
+// The inverse: w[N] to pixels x0 .. x0 + N - 1; !VEC: only pixels below lim are written.
+template <int N, bool VEC>
+__device__ __forceinline__ void store_words(uint8_t* row, int x0, int lim, const uint32_t* w) {
+    if (VEC) {
+        st_wide<4 * N>(row + (int64_t)x0 * 4, w);
+    } else {
+#pragma unroll
+        for (int j = 0; j < N; ++j)
+            if (x0 + j < lim) reinterpret_cast<uint32_t*>(row)[x0 + j] = w[j];
+    }
+}
+
 // container word <-> code value: bytes are the value; 16-bit words keep it in the high 10 bits (HIGH: NV12 at depth 10 = P010, semiplanar
 // P210 / P410) or in the low 10
 template <typename T, bool HIGH>
 __device__ __forceinline__ int dec(int w) { return sizeof(T) == 1 ? w : HIGH ? (w >> 6) : (w & 0x3ff); }
 template <typename T, bool HIGH>
 __device__ __forceinline__ int enc(int v) { return sizeof(T) == 2 && HIGH ? v << 6 : v; }
+
+// ---- host side: launching a converter kernel ---------------------------------------------------------------------------------------
+// is a pointer or a pitch a multiple of n (a power of two)?
+template <typename V> static bool al(V v, uintptr_t n) { return ((uintptr_t)v & (n - 1)) == 0; }
+
+// the grid of a kernel whose TX x TY blocks own `run` pixels per thread along each of H rows, n frames (or planes) deep
+template <int TX, int TY> static dim3 row_grid(int run, int H, int W, int n) {
+    return dim3(((W + run - 1) / run + TX - 1) / TX, (H + TY - 1) / TY, n);
+}
+
+// KERNEL<..., vec><<<grid, block, 0, stream>>>(a); the arguments after `a` are KERNEL's template arguments in front of VEC
+#define YUV_LAUNCH_VEC(KERNEL, vec, grid, block, stream, a, ...)                                   \
+    do {                                                                                           \
+        if (vec) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true>), grid, block, 0, stream, a);       \
+        else hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false>), grid, block, 0, stream, a);          \
+    } while (0)
+
+// the error of the launches since the last call, as a return code
+static int launched() {
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : (int)e;
+}
 
 }  // namespace fldr_yuv_run

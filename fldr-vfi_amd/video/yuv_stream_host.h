@@ -1,13 +1,21 @@
-// A YUV library on the model library, host side, written once: the checks of a forward's arguments, the workspace layout, the forward
-// (input conversion -> one fldr_model_forward -> n_t output conversions) and the session for streams of host frames.  Included by
-// video_host.hip (4:2:0) and ../chroma/chroma_host.hip (4:2:2, 4:4:4); each instantiates it with a traits struct L that names
+// A frame library on the model library, host side, written once: the checks of a forward's arguments, the workspace layout, the forward
+// (input conversion -> one fldr_model_forward -> n_t output conversions -> the library's pass over the outputs, if it has one), the
+// session for streams of host frames, and what the exported functions of every such library share: the two converters alone, the
+// struct sizes and the tail of the error strings.  Included first by video_host.hip (4:2:0), ../chroma/chroma_host.hip (4:2:2, 4:4:4),
+// ../pack10/pack10_host.hip (v210, Y210, Y410) and ../rgb/rgb_host.hip (RGB with alpha); each states the FrameRules of its format
+// (frame_host.h) and instantiates this text with a traits struct L : LibDefaults that names
 //   Format, Frame, Io, Config                       the library's C structs (Io and Config laid out as fldr_video_io / _session_config)
-//   E_ARG, E_FORMAT, E_WORKSPACE, E_DEVICE          its error codes (E_PLANE and E_PITCH are in its FrameRules, frame_host.h)
-//   check_format(fmt), coeffs(fmt)                  what a valid format is; its colour constants
-//   to_planar(in, fmt, pair, H, W, stream)          two frames -> the planar BGR pair
+//   E_ARG, E_FORMAT, E_WORKSPACE, E_DEVICE          its error codes (E_PLANE and E_PITCH are in its FrameRules)
+//   check_format(fmt)                               what a valid format is
+//   to_planar(in, n, fmt, planar, H, W, stream)     n (1 .. MAX_FRAMES) frames -> planar BGR [n,3,H,W]
 //   from_planar(planar, out, fmt, H, W, stream)     one planar BGR frame -> one frame
+// and, where it has them (LibDefaults has the no-op forms),
+//   check_pair(in_format, out_format)               which valid formats may meet in one forward
+//   after_outputs(io, stream)                       a pass after the n_t output conversions of a forward
+// and, where it exports the converters (libfldr_video.so does not),
+//   MAX_FRAMES                                      frames one input launch converts
 // and derives its opaque session struct from Session<L>.  Everything is in the unnamed namespace, like frame_host.h: nothing here
-// becomes a symbol of either library.  The only fldr_* functions called are those of fldr_model.h.
+// becomes a symbol of any library.  The only fldr_* functions called are those of fldr_model.h.
 #pragma once
 #include <new>
 #include <vector>
@@ -16,6 +24,12 @@
 #include "frame_host.h"
 
 namespace {
+
+// what a traits struct may leave out
+struct LibDefaults {
+    template <class Format> static int check_pair(const Format&, const Format&) { return 0; }
+    template <class Io> static int after_outputs(const Io&, hipStream_t) { return 0; }
+};
 
 // host-only checks of a forward's arguments (no model, no device)
 template <class L> int validate_io(const typename L::Io* io) {
@@ -51,6 +65,7 @@ template <class L> int64_t workspace_bytes(const fldr_model* m, int H, int W, in
 
 template <class L> int forward(const fldr_model* m, const typename L::Io* io, void* ws, int64_t ws_bytes, void* stream) {
     CK(validate_io<L>(io));
+    CK(L::check_pair(io->in_format, io->out_format));
     WsLayout lay;
     const bool in10 = deep(io->in_format), out10 = deep(io->out_format);
     const int64_t total = plan<L>(m, io->H, io->W, io->n_t, in10 ? 2 : 1, out10 ? 2 : 1, lay);
@@ -63,14 +78,14 @@ template <class L> int forward(const fldr_model* m, const typename L::Io* io, vo
     std::vector<void*> planar((size_t)io->n_t);
     for (int k = 0; k < io->n_t; ++k) planar[k] = w + lay.out + (int64_t)k * lay.out_stride;
     // the conversion writes the workspace only: if the model then refuses (a fault flag of an earlier call), no output is touched
-    CK(L::to_planar(io->in, io->in_format, pair, H, W, s));
+    CK(L::to_planar(io->in, 2, io->in_format, pair, H, W, s));
     fldr_model_io mio;
     memset(&mio, 0, sizeof(mio));
     mio.batch = 1; mio.H = H; mio.W = W; mio.input = in10 ? FLDR_MODEL_IN_U10_PLANAR : FLDR_MODEL_IN_U8_PLANAR; mio.frames_u8 = (const uint8_t*)pair;
     mio.n_t = io->n_t; mio.t = io->t; mio.output = out10 ? FLDR_MODEL_OUT_U10_PLANAR : FLDR_MODEL_OUT_U8_PLANAR; mio.out = planar.data();
     CK(fldr_model_forward(m, &mio, w + lay.model, lay.pair, stream));
     for (int k = 0; k < io->n_t; ++k) CK(L::from_planar(planar[k], io->out[k], io->out_format, H, W, s));
-    return 0;
+    return L::after_outputs(*io, s);
 }
 
 // ---- sessions -----------------------------------------------------------------------------------------------------------------
@@ -97,6 +112,7 @@ template <class L, class S> int session_create(const fldr_model* m, const typena
     if (cfg->H < 2 || cfg->W < 2 || cfg->n_t < 1 || cfg->device < 0) return L::E_ARG;
     CK(L::check_format(cfg->in_format));
     CK(L::check_format(cfg->out_format));
+    CK(L::check_pair(cfg->in_format, cfg->out_format));
     for (int i = 0; i < 4; ++i) if (cfg->reserved[i]) return L::E_FORMAT;
     if (!m) return L::E_ARG;
     const int H = cfg->H, W = cfg->W, n_t = cfg->n_t;
@@ -181,6 +197,48 @@ template <class L> int session_reset(Session<L>* s) {
     if (!s) return L::E_ARG;
     s->prev = -1;
     return 0;
+}
+
+// ---- what the exported functions share ----------------------------------------------------------------------------------------------
+// The converters alone, as a library exports them (any size from 1 x 1, any number of frames; planar BGR of 16-bit samples at an even
+// address): the checks, then one launch per MAX_FRAMES frames.
+template <class L>
+int to_planar_entry(const typename L::Frame* frames, int n_frames, const typename L::Format* format, void* planar, int H, int W, void* stream) {
+    if (!frames || !format || !planar || n_frames < 1 || H < 1 || W < 1) return L::E_ARG;
+    CK(L::check_format(*format));
+    if (deep(*format) && ((uintptr_t)planar & 1)) return L::E_ARG;
+    for (int f = 0; f < n_frames; ++f) CK(check_frame(frames[f], *format, W));
+    const int64_t frame_bytes = 3ll * H * W * (deep(*format) ? 2 : 1);
+    for (int f = 0; f < n_frames; f += L::MAX_FRAMES) {
+        const int n = n_frames - f < L::MAX_FRAMES ? n_frames - f : L::MAX_FRAMES;
+        CK(L::to_planar(frames + f, n, *format, (uint8_t*)planar + f * frame_bytes, H, W, (hipStream_t)stream));
+    }
+    return 0;
+}
+
+template <class L>
+int from_planar_entry(const void* planar, const typename L::Format* format, const typename L::Frame* out_frame, int H, int W, void* stream) {
+    if (!planar || !format || !out_frame || H < 1 || W < 1) return L::E_ARG;
+    CK(L::check_format(*format));
+    if (deep(*format) && ((uintptr_t)planar & 1)) return L::E_ARG;
+    CK(check_frame(*out_frame, *format, W));
+    return L::from_planar(planar, *out_frame, *format, H, W, (hipStream_t)stream);
+}
+
+// fldr_*_sizeof: the sizes of the four structs, for a binding to check itself against
+template <class L> int struct_sizeof(int which) {
+    switch (which) {
+    case 0: return (int)sizeof(typename L::Format);
+    case 1: return (int)sizeof(typename L::Frame);
+    case 2: return (int)sizeof(typename L::Io);
+    case 3: return (int)sizeof(typename L::Config);
+    default: return L::E_ARG;
+    }
+}
+
+// fldr_*_error_string for a code that is not the library's own: the model's, the HIP runtime's, or `unknown`
+const char* passed_error_string(int code, const char* unknown) {
+    return code > -100 && code < 0 ? fldr_model_error_string(code) : code > 0 ? hipGetErrorString((hipError_t)code) : unknown;
 }
 
 }  // namespace

@@ -183,6 +183,22 @@ def test_pitch_plane_and_argument_errors_before_any_device_call():
                 fr = io.in_[1] if side == "in" else io.out[0]
                 fr.plane[0] = fr.plane[0] + off
                 assert call(io) == want, (fmt.name, side, off)
+        # two faults at once: the plane and then the pitch by the 16-bit word, then the plane and then the pitch by the unit of 4
+        for side in ("in", "out"):
+            def two(off, pitch):
+                io = _io(V, fmt, W=W)
+                fr = io.in_[1] if side == "in" else io.out[0]
+                fr.plane[0] = fr.plane[0] + off if off is not None else None
+                fr.pitch[0] = pitch
+                return call(io)
+            assert two(2, rb - 4) == V.E_PITCH, (fmt.name, side)              # an address = 2 mod 4 and a short pitch: the pitch
+            assert two(2, rb - 2) == V.E_PITCH, (fmt.name, side)
+            assert two(1, rb - 4) == V.E_PLANE, (fmt.name, side)              # an odd address comes before any pitch
+            assert two(2, rb + 2) == (V.E_ARG if unit == 2 else V.E_PLANE), (fmt.name, side)   # both = 2 mod 4, the pitch covers the row
+            assert two(4, rb + 2) == (V.E_ARG if unit == 2 else V.E_PITCH), (fmt.name, side)
+            assert two(None, rb - 4) == V.E_PLANE, (fmt.name, side)           # a null plane and a bad pitch: the plane
+            assert two(None, rb + 2) == V.E_PLANE, (fmt.name, side)
+            assert two(None, rb + 3) == V.E_PLANE, (fmt.name, side)
         io = _io(V, fmt, W=W); io.in_[0].plane[1] = None; io.in_[0].plane[2] = None; io.in_[0].pitch[1] = io.in_[0].pitch[2] = 0
         assert call(io) == V.E_ARG                                             # only plane 0 is looked at
         io = _io(V, fmt); io.n_t = 0

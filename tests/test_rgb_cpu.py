@@ -227,6 +227,24 @@ def test_pitch_plane_and_argument_errors_before_any_device_call():
                     fr = io.in_[1] if side == "in" else io.out[0]
                     fr.plane[p] = fr.plane[p] + off
                     assert call(io) == (V.E_ARG if off % unit == 0 else V.E_PLANE), (fmt.name, fmt.depth, side, p, off)
+        # two faults at once: every plane and then every pitch by the sample size (null, too short, odd at depth 10), then every plane and
+        # then every pitch by the word layouts' unit of 4
+        for p in range(np_):
+            for side in ("in", "out"):
+                def two(off, pitch, pitch_plane=p):
+                    io = _io(V, fmt, W=W)
+                    fr = io.in_[1] if side == "in" else io.out[0]
+                    fr.plane[p] = fr.plane[p] + off if off is not None else None
+                    fr.pitch[pitch_plane] = pitch
+                    return call(io)
+                where = (fmt.name, fmt.depth, side, p)
+                assert two(2, rb - unit) == V.E_PITCH, where                   # an address = 2 mod 4 and a short pitch: the pitch
+                assert two(1, rb - unit) == (V.E_PLANE if fmt.depth == 10 else V.E_PITCH), where   # odd: a fault of 16-bit samples only
+                assert two(2, rb + 2) == (V.E_PLANE if unit == 4 else V.E_ARG), where              # both = 2 mod 4, the pitch covers the row
+                assert two(4, rb + 2) == (V.E_PITCH if unit == 4 else V.E_ARG), where
+                assert two(None, rb - unit) == V.E_PLANE, where                # a null plane and a bad pitch: the plane
+                assert two(None, rb + 1, 0) == V.E_PLANE, where                # ... whichever plane has the bad pitch
+                assert two(None, rb - unit, np_ - 1) == V.E_PLANE, where
         for p in range(np_, 4):                                                # only the layout's planes are looked at
             io = _io(V, fmt, W=W); io.in_[0].plane[p] = None; io.in_[0].pitch[p] = 0; io.out[0].plane[p] = None
             assert call(io) == V.E_ARG
