@@ -560,19 +560,24 @@ def softsplat_fused(img, flow, metric, mode, out=None, scratch=None, kernel=None
     return out
 
 
-def softsplat_acc64(imgs, flows, metrics=None, mode="softmax", want_f32=True, want_spk=False, bounds_ws=None, spk_batch=False, rows=None):
+def softsplat_acc64(imgs, flows, metrics=None, mode="softmax", want_f32=True, want_spk=False, bounds_ws=None, spk_batch=False, rows=None,
+                    whole=False, ws=None):
     """FunctionSoftsplat (softSplat.py:320-352) of one or two (img [N,C,H,W], flow [N,2,H,W]) problems of the same shape with
     destination-owned tiles and fp64 LDS atomics (fldr_softsplat_acc64): no global atomics, accumulator, memset or
     normalisation pass.  img may be a view with contiguous [H,W] planes (x_l[0][:, :, 0]); flow a batch-strided channel slice
     (up[:, :2]) whose [2,H,W] block is contiguous.  bounds_ws: per-problem bounds tables from splat_bounds_upsampled.
     spk_batch (N == 1, two problems): the packed results form ONE batch of two (sample k = problem k).
     rows: row limit — output rows at or beyond the limit, rounded up to whole tiles (24 rows for images), are left untouched.
+    whole: every tile walks the whole map, no tables (flags bit 2), whatever the size.  ws: per-problem workspaces of
+    fldr_softsplat_tile_ws_floats floats for the exact pre-pass to fill instead of ones allocated here (the caller can read the
+    tables back; maps of at most 2304 pixels take no tables and leave them untouched).
     -> list of fp32 tensors, of Spk tensors, or of (fp32, Spk); with spk_batch the two-sample Spk."""
     nd = len(imgs)
     assert 1 <= nd <= 2 and len(flows) == nd
     N, C, H, W = imgs[0].shape
     assert want_f32 or want_spk
     assert not want_spk or C > 3, "packed output needs the 16-channel configuration (C > 3)"
+    assert (bool(whole) + (bounds_ws is not None) + (ws is not None)) <= 1, "whole, bounds_ws and ws exclude each other"
     d = SplatAccDesc()
     keep, outs = [], []
     batch = None
@@ -600,12 +605,17 @@ def softsplat_acc64(imgs, flows, metrics=None, mode="softmax", want_f32=True, wa
             keep.append(mt)
         d.metric[k] = mt.data_ptr() if mt is not None else None
         if torch.is_tensor(bounds_ws):                       # one table for both problems (splat_bounds_upsampled_pair)
-            ws = bounds_ws
+            wk = bounds_ws
+        elif bounds_ws is not None:
+            wk = bounds_ws[k]
+        elif ws is not None:
+            wk = ws[k]
+            assert wk.is_cuda and wk.dtype == torch.float32 and wk.is_contiguous() and wk.numel() >= lib().fldr_softsplat_tile_ws_floats(N, H, W)
         else:
-            ws = bounds_ws[k] if bounds_ws is not None else (torch.empty(lib().fldr_softsplat_tile_ws_floats(N, H, W), device=im.device, dtype=torch.float32)
-                                                            if H * W > 2304 else None)      # (small maps: no tables, see the header)
-        keep.append(ws)
-        d.ws[k] = ws.data_ptr() if ws is not None else None
+            wk = (torch.empty(lib().fldr_softsplat_tile_ws_floats(N, H, W), device=im.device, dtype=torch.float32)
+                  if H * W > 2304 and not whole else None)               # (small maps: no tables, see the header)
+        keep.append(wk)
+        d.ws[k] = wk.data_ptr() if wk is not None else None
         o32 = torch.empty(N, C, H, W, device=im.device, dtype=torch.float32) if want_f32 else None
         if batch is not None:
             osp = batch.sample(k)
@@ -615,7 +625,7 @@ def softsplat_acc64(imgs, flows, metrics=None, mode="softmax", want_f32=True, wa
         d.out_spk[k] = osp.ptr if osp is not None else None
         outs.append((o32, osp) if (want_f32 and want_spk) else (osp if want_spk else o32))
     d.nprob, d.N, d.C, d.H, d.W, d.mode = nd, N, C, H, W, _MODES[mode]
-    d.flags = 0 if bounds_ws is None else (2 if torch.is_tensor(bounds_ws) else 1)
+    d.flags = 4 if whole else (0 if bounds_ws is None else (2 if torch.is_tensor(bounds_ws) else 1))
     d.reserved = int(rows or 0)
     assert not torch.is_tensor(bounds_ws) or nd == 2
     _check(lib().fldr_softsplat_acc64(ctypes.byref(d), _stream()), "fldr_softsplat_acc64")

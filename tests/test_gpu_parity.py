@@ -738,8 +738,9 @@ def test_gather_softsplat_matches_oracle(hip, oracle, dev, mode, shape):
 @pytest.mark.parametrize("shape", [(2, 4, 33, 70, 9.0), (1, 3, 70, 300, 40.0), (1, 13, 40, 130, 600.0), (2, 3, 130, 190, 3.0), (1, 48, 36, 60, 9.0)])
 def test_acc64_softsplat_matches_oracle(hip, oracle, dev, mode, shape):
     """fldr_softsplat_acc64 (destination-owned tiles, fp64 LDS atomics: the default splat since round 3) against the oracle:
-    image (<= 3 channels) and 16-channel-group configurations, coherent to wild flows (600 px: queue overflow -> the
-    rectangle / whole-image walks), all four modes; run-to-run identical."""
+    image (<= 3 channels) and 16-channel-group configurations, coherent to wild flows (600 px: every block of these maps matches
+    every tile; they have at most 99 blocks, so the 512-entry queue does not overflow here — tests/test_gpu_splat_ops.py reaches
+    the overflow walks), all four modes; run-to-run identical."""
     N, C, H, W, amp = shape
     g = _gen(12)
     x = torch.rand(N, C, H, W, generator=g) * 2 - 1
@@ -762,8 +763,9 @@ def test_acc64_softsplat_matches_oracle(hip, oracle, dev, mode, shape):
 def test_acc64_image_walk_of_pixel_runs(hip, hooks, oracle, dev, mode, case):
     """The image configuration's walk by runs of four adjacent source pixels (16-byte loads, neighbouring pixels' shared corners
     summed in registers, de-interleaved accumulator rows) against the oracle and against the one-pixel-per-item walk: smooth flows
-    (every hand-off taken), random ones (almost none), 600 px (queue overflow: rectangle / whole-map walks), maps small enough for
-    the table-free walk, and a smooth field with 1 % of the vectors thrown to +-3e9 px (block-queue walk)."""
+    (every hand-off taken), random ones (almost none), 600 px (every one of the map's 190 blocks matches every tile: the rectangle
+    walk over the whole map, no queue overflow — that needs more than 512 blocks, tests/test_gpu_splat_ops.py), maps small enough
+    for the table-free walk, and a smooth field with 1 % of the vectors thrown to +-3e9 px (block-queue walk)."""
     N, C, H, W, amp, kind = case
     g = _gen(77)
     x = torch.rand(N, C, H, W, generator=g) * 2 - 1
