@@ -1,13 +1,15 @@
 // libfldr_cadence.so, host side: validation, fldr_repeat_measure, and the cadence stream (container frames in, the repeats of every
 // cycle dropped, the survivors pushed into an inner fldr_rate).  The video API's rules for formats and frames, and the stream / device
 // block / pinned block the object owns, come from ../video/frame_host.h; the inner converter's configuration rules come from
-// ../rate/rate_plan.h, which includes it.  The only fldr_* functions called are those of fldr_rate.h, fldr_video.h and fldr_model.h.
+// ../rate/rate_plan.h, the checks of a luma tile measure from ../rate/tile_measure_host.h, and the cycle stream — the create prelude,
+// the drop selection, the survivors' push, flush, reset — from ../rate/cycle_stream_host.h, which includes them all.  What is here is
+// what a push uploads and measures and how its blocks are laid out.  The only fldr_* functions called are those of fldr_rate.h,
+// fldr_video.h and fldr_model.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <new>
 
-#include "../rate/rate_plan.h"
+#include "../rate/cycle_stream_host.h"
 #include "cadence_internal.h"
 
 using namespace fldr_cadence_impl;
@@ -28,15 +30,12 @@ int resolve_params(const fldr_repeat_params* p, int& tile_sad_min) {
 
 int check_measure(int H, int W, const fldr_video_format* fmt, const fldr_video_frame in[2], const fldr_repeat_params* p, void* state,
                   int& tile_sad_min) {
-    const int64_t T = FLDR_REPEAT_TILE;
-    if (!fmt || !in || H < 1 || W < 1 || H > 0x7fffffff - T || W > 0x7fffffff - T) return FLDR_CADENCE_E_ARG;   // rows and columns rounded up to whole tiles stay inside 32 bits
-    if (((int64_t)W + T - 1) / T * (((int64_t)H + T - 1) / T) > 0x7fffffffll) return FLDR_CADENCE_E_ARG;   // the key holds the tile index in 31 bits
+    if (!fmt || !in || !tiles_ok(H, W, FLDR_REPEAT_TILE)) return FLDR_CADENCE_E_ARG;
     int rc = resolve_params(p, tile_sad_min);
     if (!rc) rc = check_format(*fmt);
     for (int f = 0; f < 2 && !rc; ++f) rc = check_frame(in[f], *fmt, W);
     if (rc) return rc;
-    if (!state || ((uintptr_t)state & (ALIGN - 1))) return FLDR_CADENCE_E_STATE;
-    return 0;
+    return check_state(state, FLDR_CADENCE_E_STATE);
 }
 
 int enqueue_measure(int H, int W, const fldr_video_format& fmt, const fldr_video_frame in[2], int tile_sad_min, void* state, hipStream_t s) {
@@ -44,24 +43,16 @@ int enqueue_measure(int H, int W, const fldr_video_format& fmt, const fldr_video
                           state, s);
 }
 
-bool cycle_ok(const fldr_cadence_config& c) {
-    return c.cycle >= 1 && c.cycle <= FLDR_CADENCE_MAX_CYCLE && c.drop >= 0 && c.drop < c.cycle;
-}
-
-// in_num (cycle - drop) / (in_den cycle), reduced; FLDR_RATE_E_RATIO when a term does not fit int32
-int inner_rate(const fldr_cadence_config& c, int32_t& num, int32_t& den) {
-    if (c.rate.in_num <= 0 || c.rate.in_den <= 0) return FLDR_RATE_E_RATIO;
-    int64_t n = (int64_t)c.rate.in_num * (c.cycle - c.drop), d = (int64_t)c.rate.in_den * c.cycle;
-    reduce_terms(n, d);
-    if (n > 0x7fffffffll || d > 0x7fffffffll) return FLDR_RATE_E_RATIO;
-    num = (int32_t)n; den = (int32_t)d;
-    return 0;
-}
-
-// (max_tile_sad, sad) of a before that of b
-bool key_less(const fldr_repeat_result& a, const fldr_repeat_result& b) {
-    return a.max_tile_sad != b.max_tile_sad ? a.max_tile_sad < b.max_tile_sad : a.sad < b.sad;
-}
+// the cycle stream's view of this library (../rate/cycle_stream_host.h)
+struct CadenceCycle {
+    using Config = fldr_cadence_config;
+    using Result = fldr_repeat_result;
+    using Report = fldr_cadence_report;
+    static constexpr int E_ARG = FLDR_CADENCE_E_ARG, E_DEVICE = FLDR_CADENCE_E_DEVICE, MAX_CYCLE = FLDR_CADENCE_MAX_CYCLE;
+    // (max_tile_sad, sad) of a before that of b
+    static bool key_less(const Result& a, const Result& b) { return a.max_tile_sad != b.max_tile_sad ? a.max_tile_sad < b.max_tile_sad : a.sad < b.sad; }
+    static bool report_frame(Report&, int, const Result& res) { return !res.repeat; }
+};
 
 }  // namespace
 
@@ -96,124 +87,37 @@ extern "C" FLDR_CADENCE_API int fldr_repeat_measure(int H, int W, const fldr_vid
 }
 
 // ---- the stream ------------------------------------------------------------------------------------------------------------------------
-struct fldr_cadence {
-    fldr_cadence_config cfg;
-    fldr_rate* inner;
-    int inner_max, max_out;
-    // device: slot 0, slot 1, the repeat state.  pinned: a ring of `cycle` packed frames, then `cycle` results.
-    StreamMem sm;
-    int64_t frame_bytes;
+struct fldr_cadence : CycleStream<CadenceCycle> {
+    // device: slot 0, slot 1, the repeat state.  pinned: the ring of `cycle` packed frames as they came, then the `cycle` results.
     uint8_t* slot[2];
     void* state_dev;
-    uint8_t* ring;
-    fldr_repeat_result* result_host;
     int prev;                          // slot holding the previous frame, -1 when none
-    int64_t n;                         // frames pushed since create / reset
-    int m;                             // frames of the current cycle in the ring
-    bool keyed[FLDR_CADENCE_MAX_CYCLE];   // ring frame k has a key (it is not frame 0 of the stream)
+    void forget_own() { prev = -1; }
 };
 
-namespace {
-
-void forget(fldr_cadence* c) {
-    c->prev = -1; c->n = 0; c->m = 0;
-    (void)fldr_rate_reset(c->inner);
-}
-
-uint8_t* ring_frame(const fldr_cadence* c, int k) { return c->ring + k * c->frame_bytes; }
-
-// The ring holds m frames whose measures have been enqueued: wait, drop n_drop of them, push the others into the inner converter.
-// On a failure the object has been reset.
-int finish_cycle(fldr_cadence* c, int n_drop, const fldr_video_frame* host_outs, int* n_out, fldr_cadence_report* report) {
-    const fldr_rate_config& rc = c->cfg.rate;
-    const int m = c->m;
-    const hipError_t e = hipStreamSynchronize(c->sm.stream);
-    if (e != hipSuccess) { forget(c); return (int)e; }
-    uint32_t dropped = 0;
-    for (int d = 0; d < n_drop; ++d) {                                 // the smallest key not yet taken, the lowest frame among equals
-        int best = -1;
-        for (int k = 0; k < m; ++k) {
-            if (!c->keyed[k] || (dropped >> k & 1u)) continue;
-            if (best < 0 || key_less(c->result_host[k], c->result_host[best])) best = k;
-        }
-        if (best < 0) break;
-        dropped |= 1u << best;
-    }
-    fldr_cadence_report rep;
-    memset(&rep, 0, sizeof(rep));
-    rep.first_frame = c->n - m;
-    rep.n_frames = (uint32_t)m;
-    rep.dropped_mask = dropped;
-    int total = 0, survivor = 0;
-    for (int k = 0; k < m; ++k) {
-        rep.measure[k] = c->result_host[k];
-        if (dropped >> k & 1u) { if (!rep.measure[k].repeat) ++rep.moving_dropped; continue; }
-        if (c->keyed[k] && rep.measure[k].repeat) ++rep.still_kept;
-        const fldr_video_frame fr = packed(ring_frame(c, k), rc.format, rc.H, rc.W);
-        fldr_scene_result scene;
-        int got = 0;
-        const int r = fldr_rate_push(c->inner, &fr, host_outs + total, &got, &scene);
-        if (r) { forget(c); *n_out = 0; return r; }
-        if (scene.cut) rep.cut_mask |= 1u << survivor;
-        total += got;
-        ++survivor;
-    }
-    c->m = 0;
-    *n_out = total;
-    if (report) *report = rep;
-    return 0;
-}
-
-int check_outs(const fldr_cadence* c, const fldr_video_frame* host_outs) {
-    if (!host_outs) return FLDR_CADENCE_E_ARG;
-    for (int k = 0; k < c->max_out; ++k) CK(check_frame(host_outs[k], c->cfg.rate.format, c->cfg.rate.W));
-    return 0;
-}
-
-}  // namespace
-
 extern "C" FLDR_CADENCE_API int fldr_cadence_inner_rate(const fldr_cadence_config* cfg, int32_t* num, int32_t* den) {
-    if (!cfg || !num || !den || !cycle_ok(*cfg)) return FLDR_CADENCE_E_ARG;
-    return inner_rate(*cfg, *num, *den);
+    return inner_rate_entry<CadenceCycle>(cfg, num, den);
 }
 
 extern "C" FLDR_CADENCE_API int fldr_cadence_create(const fldr_model* m, const fldr_cadence_config* ccfg, fldr_cadence** out) {
-    if (!ccfg || !out) return FLDR_CADENCE_E_ARG;
-    *out = nullptr;
-    // fldr_rate_create's checks, in its order and with its codes (../rate/rate_plan.h); cycle and drop are judged between them and its ratio limits
-    const fldr_rate_config* cfg = &ccfg->rate;
-    CK(check_rate_config(*cfg));
-    // this library's
-    if (!cycle_ok(*ccfg)) return FLDR_CADENCE_E_ARG;
-    int tile_sad_min;
-    CK(resolve_params(&ccfg->repeat, tile_sad_min));
-    if (ccfg->reserved[0] || ccfg->reserved[1]) return FLDR_CADENCE_E_ARG;
-    // the inner converter's configuration, and fldr_rate_create's limits on its ratio
-    fldr_rate_config icfg = *cfg;
-    CK(inner_rate(*ccfg, icfg.in_num, icfg.in_den));
-    RatePlan plan;                                                     // only the limits are wanted: the inner converter makes its own
-    CK(reduce_rate(icfg.in_num, icfg.in_den, icfg.out_num, icfg.out_den, plan));
-    if (!m) return FLDR_CADENCE_E_ARG;
-    fldr_cadence* c = new (std::nothrow) fldr_cadence();
-    if (!c) return FLDR_CADENCE_E_DEVICE;
-    c->cfg = *ccfg;
-    c->inner = nullptr;
-    const int rc = fldr_rate_create(m, &icfg, &c->inner);
-    if (rc) { delete c; return rc; }
-    c->inner_max = fldr_rate_max_out(c->inner);
-    c->max_out = (ccfg->cycle - ccfg->drop) * c->inner_max + 1;
-    c->frame_bytes = align_up(packed_bytes(cfg->format, cfg->H, cfg->W));
-    const int64_t dev_total = 2 * c->frame_bytes + FLDR_REPEAT_STATE_BYTES;
-    const int64_t host_total = ccfg->cycle * c->frame_bytes + align_up(ccfg->cycle * RESULT_BYTES);
-    if (!open_stream_mem(c->sm, cfg->device, dev_total, host_total)) { fldr_rate_destroy(c->inner); delete c; return FLDR_CADENCE_E_DEVICE; }
-    c->slot[0] = c->sm.dev;
-    c->slot[1] = c->slot[0] + c->frame_bytes;
-    c->state_dev = c->slot[1] + c->frame_bytes;
-    c->ring = c->sm.pinned;
-    c->result_host = (fldr_repeat_result*)(c->ring + ccfg->cycle * c->frame_bytes);
-    c->prev = -1; c->n = 0; c->m = 0;
-    *out = c;
-    return 0;
+    return cycle_create<CadenceCycle>(m, ccfg, out,
+        [](const fldr_cadence_config& cc) {
+            int tile_sad_min;
+            CK(resolve_params(&cc.repeat, tile_sad_min));
+            return cc.reserved[0] || cc.reserved[1] ? FLDR_CADENCE_E_ARG : 0;
+        },
+        [](fldr_cadence* c) {
+            const int cycle = c->cfg.cycle;
+            const int64_t dev_total = 2 * c->frame_bytes + FLDR_REPEAT_STATE_BYTES;
+            const int64_t host_total = cycle * c->frame_bytes + align_up(cycle * RESULT_BYTES);
+            if (!open_stream_mem(c->sm, c->cfg.rate.device, dev_total, host_total)) return false;
+            c->slot[0] = c->sm.dev;
+            c->slot[1] = c->slot[0] + c->frame_bytes;
+            c->state_dev = c->slot[1] + c->frame_bytes;
+            c->ring = c->sm.pinned;
+            c->result_host = (fldr_repeat_result*)(c->ring + cycle * c->frame_bytes);
+            return true;
+        });
 }
 
 extern "C" FLDR_CADENCE_API int fldr_cadence_max_out(const fldr_cadence* c) { return c ? c->max_out : FLDR_CADENCE_E_ARG; }
@@ -228,7 +132,7 @@ extern "C" FLDR_CADENCE_API int fldr_cadence_push(fldr_cadence* c, const fldr_vi
     const fldr_video_format& fmt = rc.format;
     CK(check_frame(*frame, fmt, W));
     const bool completes = c->m + 1 == c->cfg.cycle;
-    if (completes) CK(check_outs(c, host_outs));
+    if (completes) CK(check_outs<CadenceCycle>(c, host_outs));
     DeviceGuard g(c->sm.device);
     if (!g.ok) return FLDR_CADENCE_E_DEVICE;
     const hipStream_t stream = c->sm.stream;
@@ -247,40 +151,17 @@ extern "C" FLDR_CADENCE_API int fldr_cadence_push(fldr_cadence* c, const fldr_vi
             if (e != hipSuccess) r = (int)e;
         }
     }
-    if (r) { (void)hipStreamSynchronize(stream); (void)hipGetLastError(); forget(c); return r; }
+    if (r) return fail(c, r);
     c->prev = cur;
     c->n += 1;
     c->m += 1;
-    return completes ? finish_cycle(c, c->cfg.drop, host_outs, n_out, report) : 0;
+    return completes ? finish_cycle<CadenceCycle>(c, c->n - c->m, c->cfg.drop, host_outs, n_out, report) : 0;
 }
 
 extern "C" FLDR_CADENCE_API int fldr_cadence_flush(fldr_cadence* c, const fldr_video_frame* host_outs, int* n_out, fldr_cadence_report* report) {
-    if (!c || !n_out) return FLDR_CADENCE_E_ARG;
-    *n_out = 0;
-    if (report) memset(report, 0, sizeof(*report));
-    CK(check_outs(c, host_outs));
-    DeviceGuard g(c->sm.device);
-    if (!g.ok) return FLDR_CADENCE_E_DEVICE;
-    int total = 0;
-    if (c->m) CK(finish_cycle(c, c->m * c->cfg.drop / c->cfg.cycle, host_outs, &total, report));
-    int got = 0;
-    const int r = fldr_rate_flush(c->inner, host_outs + total, &got);
-    if (r) { forget(c); return r; }
-    *n_out = total + got;
-    return 0;
+    return cycle_flush<CadenceCycle>(c, host_outs, n_out, report, [](fldr_cadence*) { return 0; });
 }
 
-extern "C" FLDR_CADENCE_API int fldr_cadence_reset(fldr_cadence* c) {
-    if (!c) return FLDR_CADENCE_E_ARG;
-    DeviceGuard g(c->sm.device);
-    if (g.ok) { (void)hipStreamSynchronize(c->sm.stream); (void)hipGetLastError(); }   // nothing enqueued may still write the pinned results
-    forget(c);
-    return 0;
-}
+extern "C" FLDR_CADENCE_API int fldr_cadence_reset(fldr_cadence* c) { return cycle_reset<CadenceCycle>(c); }
 
-extern "C" FLDR_CADENCE_API void fldr_cadence_destroy(fldr_cadence* c) {
-    if (!c) return;
-    fldr_rate_destroy(c->inner);
-    close_stream_mem(c->sm);
-    delete c;
-}
+extern "C" FLDR_CADENCE_API void fldr_cadence_destroy(fldr_cadence* c) { cycle_destroy(c); }

@@ -6,14 +6,10 @@
 // read whole 128-byte lines of each row.  The 16-byte loads need both plane addresses and pitches 16-byte aligned (VEC); the same
 // arithmetic runs on per-sample loads otherwise, and the bytes of a row behind its last whole 16 go sample by sample in either form.
 // Per 16 bytes: v_sad_u8 on the dwords (depth 8) or v_sad_u16 on the words reduced to 8 bits (depth 10).  A tile's sum is reduced
-// inside its wave; each wave keeps the sum, the maximum key and the count of its tiles in registers, the workgroup combines its
-// waves in LDS, and one lane adds the workgroup's three words to memory with integer atomics.  For the maximum one 64-bit atomicMax
-// on (tile_sad << 32) | (0xffffffff - index) gives the lowest index among equal maxima.  Every word is an integer sum, maximum or
-// count, so the order of the atomics does not show in the result.  No float anywhere.
-//
-// A workgroup's atomics do not go to one address for the whole grid (2040 workgroups at 3840 x 2160): the state holds STATE_SLOTS
-// accumulator slots, each on a 64-byte line of its own, a workgroup adds to the slot of its number, and the result kernel's lanes
-// combine the slots.  INTEGRATION.md section 3h has the measurement of both forms.
+// inside its wave; each wave keeps the sum, the maximum key and the count of its tiles in registers.  What becomes of those three
+// words — the key, the workgroup's slot of the state, the atomics, the grid — is the tile reduce of ../rate/tile_reduce_device.h,
+// here with one sum, one key and one count; the meeting of the waves in LDS and the result kernel's gather, which it describes, are
+// written out below.  No float anywhere.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -21,9 +17,8 @@
 
 namespace fldr_cadence_impl {
 
-#define RK_THREADS 256
-#define RK_WAVES (RK_THREADS / 64)
-#define RK_MAX_BLOCKS 2048       // 8 workgroups per CU of an MI355X; larger frames walk with the grid's strides
+#define RK_THREADS THREADS
+#define RK_WAVES WAVES
 #define RK_TILE FLDR_REPEAT_TILE
 
 struct RepeatArgs {
@@ -36,9 +31,7 @@ struct RepeatArgs {
     uint8_t* state;
 };
 
-__global__ __launch_bounds__(RK_THREADS) void repeat_zero_kernel(uint8_t* state) {
-    reinterpret_cast<uint4*>(state)[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);          // 256 x 16 = FLDR_REPEAT_STATE_BYTES
-}
+__global__ __launch_bounds__(RK_THREADS) void repeat_zero_kernel(uint8_t* state) { zero_state<FLDR_REPEAT_STATE_BYTES>(state); }
 
 template <int MODE, bool VEC>
 __global__ __launch_bounds__(RK_THREADS) void repeat_tiles_kernel(RepeatArgs a) {
@@ -80,8 +73,7 @@ __global__ __launch_bounds__(RK_THREADS) void repeat_tiles_kernel(RepeatArgs a) 
 #pragma unroll
         for (int m = 32; m >= 1; m >>= 1) sad += (uint32_t)__shfl_xor((int)sad, m, 64);      // the tile's sum, in every lane
         sum += sad;
-        const unsigned long long k = ((unsigned long long)sad << 32) | (unsigned long long)(0xffffffffu - tile);
-        key = k > key ? k : key;
+        key = max64(pack_key(sad, key_low(tile)), key);
         moving += sad >= a.tile_sad_min ? 1u : 0u;
     }
     if (lane == 0) { w_sad[wave] = sum; w_key[wave] = key; w_moving[wave] = moving; }
@@ -90,20 +82,19 @@ __global__ __launch_bounds__(RK_THREADS) void repeat_tiles_kernel(RepeatArgs a) 
 #pragma unroll
         for (int w = 1; w < RK_WAVES; ++w) {
             sum += w_sad[w];
-            key = w_key[w] > key ? w_key[w] : key;
+            key = max64(w_key[w], key);
             moving += w_moving[w];
         }
-        // a wave without a tile holds key 0, below every tile's key: the low word of a key is never 0 (tile < 2^31)
-        uint8_t* slot = a.state + STATE_SLOT_BYTES * (1 + (blockIdx.y * gridDim.x + blockIdx.x) % STATE_SLOTS);
-        if (sum) atomicAdd(reinterpret_cast<unsigned long long*>(slot + SLOT_SAD_OFFSET), sum);
-        atomicMax(reinterpret_cast<unsigned long long*>(slot + SLOT_KEY_OFFSET), key);
-        if (moving) atomicAdd(reinterpret_cast<uint32_t*>(slot + SLOT_MOVING_OFFSET), moving);
+        uint8_t* slot = slot_of<STATE_SLOT_BYTES>(a.state);
+        slot_add(slot_u64(slot, SLOT_SAD_OFFSET), sum);
+        slot_max(slot_u64(slot, SLOT_KEY_OFFSET), key);
+        slot_add(reinterpret_cast<uint32_t*>(slot + SLOT_MOVING_OFFSET), moving);
     }
 }
 
 // one wave: lane l >= 1 takes slot l (line 0 of the state is the result), the wave combines them, lane 0 writes
 __global__ __launch_bounds__(64) void repeat_result_kernel(uint8_t* state) {
-    static_assert(STATE_SLOTS == 63 && STATE_SLOT_BYTES * (STATE_SLOTS + 1) == FLDR_REPEAT_STATE_BYTES, "one slot per lane but lane 0");
+    static_assert(STATE_SLOT_BYTES * (SLOTS + 1) == FLDR_REPEAT_STATE_BYTES, "one slot per lane but lane 0");
     const int lane = threadIdx.x;
     const uint8_t* slot = state + STATE_SLOT_BYTES * lane;
     unsigned long long sad = lane ? *reinterpret_cast<const unsigned long long*>(slot + SLOT_SAD_OFFSET) : 0ull;
@@ -112,15 +103,14 @@ __global__ __launch_bounds__(64) void repeat_result_kernel(uint8_t* state) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) {
         sad += __shfl_xor(sad, m, 64);
-        const unsigned long long k = __shfl_xor(key, m, 64);
-        key = k > key ? k : key;
+        key = max64(__shfl_xor(key, m, 64), key);
         moving += (uint32_t)__shfl_xor((int)moving, m, 64);
     }
     if (lane != 0) return;
     fldr_repeat_result* r = reinterpret_cast<fldr_repeat_result*>(state);
     r->sad = sad;
-    r->max_tile_sad = (uint32_t)(key >> 32);
-    r->max_tile = 0xffffffffu - (uint32_t)key;
+    r->max_tile_sad = key_value(key);
+    r->max_tile = key_index(key);
     r->moving_tiles = moving;
     r->repeat = moving == 0u ? 1u : 0u;
     r->reserved[0] = r->reserved[1] = 0u;
@@ -133,14 +123,12 @@ int repeat_measure(const void* y0, int64_t pitch0, const void* y1, int64_t pitch
     a.pitch[0] = pitch0; a.pitch[1] = pitch1;
     a.row_bytes = luma_row_bytes(W, mode);
     a.H = H;
-    a.tiles_x = (uint32_t)((W + RK_TILE - 1) / RK_TILE);
-    a.tiles_y = (uint32_t)((H + RK_TILE - 1) / RK_TILE);
+    a.tiles_x = tiles_of(W, RK_TILE);
+    a.tiles_y = tiles_of(H, RK_TILE);
     a.tile_sad_min = (uint32_t)tile_sad_min;
     a.state = (uint8_t*)state;
     const bool vec = luma_vec_ok(y0, pitch0, y1, pitch1);
-    // every workgroup's wave 0 has a tile: blockIdx.x * RK_WAVES < tiles_x and blockIdx.y < tiles_y
-    const uint32_t bx = min((a.tiles_x + RK_WAVES - 1) / RK_WAVES, (uint32_t)RK_MAX_BLOCKS);
-    const dim3 blocks(bx, min(a.tiles_y, (uint32_t)RK_MAX_BLOCKS / bx));
+    const dim3 blocks = tile_grid(a.tiles_x, a.tiles_y);                // a wave's column is a tile
     repeat_zero_kernel<<<1, RK_THREADS, 0, stream>>>(a.state);
     SAMPLE16_LAUNCH(repeat_tiles_kernel, mode, vec, blocks, RK_THREADS, stream, a);
     repeat_result_kernel<<<1, 64, 0, stream>>>(a.state);

@@ -10,14 +10,11 @@ tuples of 2-D plane tensors (device) or numpy arrays (host).  repeat_measure enq
 read the result back unless told not to).  No fallback: a missing library raises at load.
 """
 import ctypes
+import functools
 import os
 
-import torch
-
-import fldr_model
 import fldr_rate
-import fldr_video
-from fldr_rate import RateConfig, _rate, rate_config
+from fldr_rate import RateConfig, inner_rate, rate_config  # noqa: F401  (inner_rate: the pure-Python statement of fldr_cadence_inner_rate)
 from fldr_video import Format, Frame, _stream_ptr, frame_struct
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -80,54 +77,14 @@ _SIGNATURES = {
     "fldr_cadence_destroy": (None, [ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
-_lib = None
-
-
-class CadenceError(RuntimeError):
-    def __init__(self, what, code):
-        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_cadence_error_string(code).decode(), code))
-        self.code = code
-
-
-def lib():
-    """The loaded libfldr_cadence.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
-    global _lib
-    if _lib is None:
-        fldr_rate.lib()
-        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (RepeatParams, RepeatResult, CadenceConfig, Report), "fldr_cadence", CADENCE_VERSION)
-    return _lib
-
-
-def _check(code, what):
-    if code != 0:
-        raise CadenceError(what, code)
-
-
-def inner_rate(in_rate, cycle, drop):
-    """The input rate of the inner converter: in_rate x (cycle - drop) / cycle, a Fraction."""
-    return _rate(in_rate) * (int(cycle) - int(drop)) / int(cycle)
-
-
-def inner_rate_raw(in_num, in_den, cycle, drop):
-    """fldr_cadence_inner_rate -> (code, num, den); does not raise."""
-    cfg = CadenceConfig()
-    cfg.rate.in_num, cfg.rate.in_den, cfg.cycle, cfg.drop = int(in_num), int(in_den), int(cycle), int(drop)
-    n, d = ctypes.c_int32(0), ctypes.c_int32(0)
-    return lib().fldr_cadence_inner_rate(ctypes.byref(cfg), ctypes.byref(n), ctypes.byref(d)), n.value, d.value
+_API = fldr_rate.Binding("cadence", LIB_PATH, CADENCE_VERSION, _SIGNATURES, (RepeatParams, RepeatResult, CadenceConfig, Report), "CadenceError")
+CadenceError, lib, _check = _API.Error, _API.lib, _API.check
+inner_rate_raw = functools.partial(fldr_rate.inner_rate_raw, _API, CadenceConfig)
 
 
 # ---- the repeat measure --------------------------------------------------------------------------------------------------------------
-def repeat_state(device):
-    """FLDR_REPEAT_STATE_BYTES of device memory (torch's allocations are 256-byte aligned)."""
-    return torch.empty(REPEAT_STATE_BYTES, dtype=torch.uint8, device=device)
-
-
-def read_result(state):
-    """The fldr_repeat_result at the start of a repeat state tensor (synchronising copy) -> dict; "reserved" holds the two spare words."""
-    r = RepeatResult.from_buffer_copy(state[:ctypes.sizeof(RepeatResult)].cpu().numpy().tobytes())
-    d = r.as_dict()
-    d["reserved"] = [int(v) for v in r.reserved]
-    return d
+repeat_state = functools.partial(fldr_rate.state_tensor, REPEAT_STATE_BYTES)      # (device) -> FLDR_REPEAT_STATE_BYTES of device memory
+read_result = functools.partial(fldr_rate.read_struct, RepeatResult)               # (state) -> the fldr_repeat_result at its start, a dict
 
 
 def repeat_measure_raw(H, W, fmt, frames, params, state_ptr, stream_ptr):
@@ -161,42 +118,12 @@ def make_config(H, W, fmt, in_rate, out_rate, cycle, drop, scene=True, device=0,
     return cfg
 
 
-class Cadence(fldr_video.HostStream):
+class Cadence(fldr_rate.CycleStream):
     """fldr_cadence: container frames (tuples of numpy planes) pushed one by one at in_rate, of every `cycle` of which `drop` are
-    repeats; the push that completes a cycle returns the output frames at out_rate its survivors produce, flush() those of the partial
-    last cycle and the inner converter's flush."""
-
-    _destroy = staticmethod(lambda h: lib().fldr_cadence_destroy(h))
+    repeats; push, flush, reset and last_report are fldr_rate.CycleStream's."""
+    _api, _Report = _API, Report
 
     def __init__(self, native_model, H, W, fmt=None, in_rate=60, out_rate=120, cycle=5, drop=3, scene=True, params=None, tile_sad_min=0):
         fmt = fmt or Format()
         cfg = make_config(H, W, fmt, in_rate, out_rate, cycle, drop, scene, native_model.device.index or 0, params, tile_sad_min)
-        self._h = ctypes.c_void_p()
-        self.model = native_model                                    # the stream uses the model: keep it alive
-        _check(lib().fldr_cadence_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_cadence_create")
-        self.H, self.W, self.format, self.cycle, self.drop = int(H), int(W), fmt, int(cycle), int(drop)
-        self.max_out = lib().fldr_cadence_max_out(self._h)
-        self._stage(fmt, H, W, self.max_out)
-        self.last_report = None
-
-    def _done(self, n, rep):
-        self.last_report = rep.as_dict() if rep.n_frames else None
-        return self._taken(n)
-
-    def push(self, frame):
-        """-> the list of output frames due (tuples of numpy planes, fresh copies): empty unless the frame completes a cycle;
-        self.last_report: that cycle's report dict, else None."""
-        fr = frame_struct(frame)
-        n = ctypes.c_int(-1)
-        rep = Report()
-        _check(lib().fldr_cadence_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n), ctypes.byref(rep)), "fldr_cadence_push")
-        return self._done(n.value, rep)
-
-    def flush(self):
-        n = ctypes.c_int(-1)
-        rep = Report()
-        _check(lib().fldr_cadence_flush(self._h, self._out_structs(), ctypes.byref(n), ctypes.byref(rep)), "fldr_cadence_flush")
-        return self._done(n.value, rep)
-
-    def reset(self):
-        _check(lib().fldr_cadence_reset(self._h), "fldr_cadence_reset")
+        self._create(native_model, cfg, H, W, fmt, cycle, drop)

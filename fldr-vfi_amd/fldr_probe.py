@@ -11,13 +11,11 @@ Frames are fldr_video's: tuples of 2-D plane tensors (device) or numpy arrays (h
 (and synchronises to read the result back unless told not to).  No fallback: a missing library raises at load.
 """
 import ctypes
+import functools
 import os
 
-import torch
-
-import fldr_model
 import fldr_rate
-from fldr_rate import E_ARG, E_DEVICE, E_STATE  # noqa: F401  (this library's codes are the rate library's)
+from fldr_rate import E_ARG, E_DEVICE, E_STATE, _ref  # noqa: F401  (this library's codes are the rate library's)
 from fldr_video import Format, Frame, _stream_ptr, frame_struct
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -109,45 +107,13 @@ _SIGNATURES = {
     "fldr_probe_destroy": (None, [ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
-_lib = None
-
-
-class ProbeError(RuntimeError):
-    def __init__(self, what, code):
-        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_probe_error_string(code).decode(), code))
-        self.code = code
-
-
-def lib():
-    """The loaded libfldr_probe.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
-    global _lib
-    if _lib is None:
-        fldr_rate.lib()
-        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (Params, Result, Verdict, ProbeConfig), "fldr_probe", PROBE_VERSION)
-    return _lib
-
-
-def _check(code, what):
-    if code != 0:
-        raise ProbeError(what, code)
-
-
-def _ref(x):
-    return ctypes.byref(x) if x is not None else None
+_API = fldr_rate.Binding("probe", LIB_PATH, PROBE_VERSION, _SIGNATURES, (Params, Result, Verdict, ProbeConfig), "ProbeError")
+ProbeError, lib, _check = _API.Error, _API.lib, _API.check
 
 
 # ---- the measure -----------------------------------------------------------------------------------------------------------------------
-def measure_state(device):
-    """FLDR_PROBE_STATE_BYTES of device memory (torch's allocations are 256-byte aligned)."""
-    return torch.empty(STATE_BYTES, dtype=torch.uint8, device=device)
-
-
-def read_result(state):
-    """The fldr_probe_result at the start of a measure state tensor (synchronising copy) -> dict; "reserved" holds the spare words."""
-    r = Result.from_buffer_copy(state[:ctypes.sizeof(Result)].cpu().numpy().tobytes())
-    d = r.as_dict()
-    d["reserved"] = [int(v) for v in r.reserved]
-    return d
+measure_state = functools.partial(fldr_rate.state_tensor, STATE_BYTES)             # (device) -> FLDR_PROBE_STATE_BYTES of device memory
+read_result = functools.partial(fldr_rate.read_struct, Result)                     # (state) -> the fldr_probe_result at its start, a dict
 
 
 def measure_raw(H, W, fmt, cur, prev, nxt, params, state_ptr, stream_ptr):

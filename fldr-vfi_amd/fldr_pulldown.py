@@ -12,14 +12,11 @@ tuples of 2-D plane tensors (device) or numpy arrays (host).  measure and assemb
 synchronises to read the result back unless told not to).  No fallback: a missing library raises at load.
 """
 import ctypes
+import functools
 import os
 
-import torch
-
-import fldr_model
 import fldr_rate
-import fldr_video
-from fldr_rate import E_ARG, E_DEVICE, E_RATIO, E_STATE, RateConfig, _rate, rate_config  # noqa: F401  (this library's codes are the rate library's)
+from fldr_rate import E_ARG, E_DEVICE, E_RATIO, E_STATE, RateConfig, _ref, inner_rate, rate_config  # noqa: F401  (this library's codes are the rate library's)
 from fldr_video import Format, Frame, _stream_ptr, frame_struct
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -88,58 +85,14 @@ _SIGNATURES = {
     "fldr_pulldown_destroy": (None, [ctypes.c_void_p]),
 }
 EXPORTS = tuple(_SIGNATURES)
-_lib = None
-
-
-class PulldownError(RuntimeError):
-    def __init__(self, what, code):
-        super().__init__("%s failed: %s (code %d)" % (what, lib().fldr_pulldown_error_string(code).decode(), code))
-        self.code = code
-
-
-def lib():
-    """The loaded libfldr_pulldown.so, checked against this binding (struct sizes, header version); raises when it has not been built."""
-    global _lib
-    if _lib is None:
-        fldr_rate.lib()
-        _lib = fldr_model.load_library(LIB_PATH, _SIGNATURES, (Params, Result, PulldownConfig, Report), "fldr_pulldown", PULLDOWN_VERSION)
-    return _lib
-
-
-def _check(code, what):
-    if code != 0:
-        raise PulldownError(what, code)
-
-
-def inner_rate(in_rate, cycle, drop):
-    """The input rate of the inner converter: in_rate x (cycle - drop) / cycle, a Fraction."""
-    return _rate(in_rate) * (int(cycle) - int(drop)) / int(cycle)
-
-
-def inner_rate_raw(in_num, in_den, cycle, drop):
-    """fldr_pulldown_inner_rate -> (code, num, den); does not raise."""
-    cfg = PulldownConfig()
-    cfg.rate.in_num, cfg.rate.in_den, cfg.cycle, cfg.drop = int(in_num), int(in_den), int(cycle), int(drop)
-    n, d = ctypes.c_int32(0), ctypes.c_int32(0)
-    return lib().fldr_pulldown_inner_rate(ctypes.byref(cfg), ctypes.byref(n), ctypes.byref(d)), n.value, d.value
-
-
-def _ref(x):
-    return ctypes.byref(x) if x is not None else None
+_API = fldr_rate.Binding("pulldown", LIB_PATH, PULLDOWN_VERSION, _SIGNATURES, (Params, Result, PulldownConfig, Report), "PulldownError")
+PulldownError, lib, _check = _API.Error, _API.lib, _API.check
+inner_rate_raw = functools.partial(fldr_rate.inner_rate_raw, _API, PulldownConfig)
 
 
 # ---- the measure -----------------------------------------------------------------------------------------------------------------------
-def measure_state(device):
-    """FLDR_PULLDOWN_STATE_BYTES of device memory (torch's allocations are 256-byte aligned)."""
-    return torch.empty(STATE_BYTES, dtype=torch.uint8, device=device)
-
-
-def read_result(state):
-    """The fldr_pulldown_result at the start of a measure state tensor (synchronising copy) -> dict; "reserved" holds the five spare words."""
-    r = Result.from_buffer_copy(state[:ctypes.sizeof(Result)].cpu().numpy().tobytes())
-    d = r.as_dict()
-    d["reserved"] = [int(v) for v in r.reserved]
-    return d
+measure_state = functools.partial(fldr_rate.state_tensor, STATE_BYTES)             # (device) -> FLDR_PULLDOWN_STATE_BYTES of device memory
+read_result = functools.partial(fldr_rate.read_struct, Result)                     # (state) -> the fldr_pulldown_result at its start, a dict
 
 
 def measure_raw(H, W, fmt, cur, prev, nxt, anchor, params, state_ptr, stream_ptr):
@@ -189,43 +142,13 @@ def make_config(H, W, fmt, in_rate, out_rate, cycle, drop, anchor=0, post=POST_K
     return cfg
 
 
-class Pulldown(fldr_video.HostStream):
+class Pulldown(fldr_rate.CycleStream):
     """fldr_pulldown: woven container frames (tuples of numpy planes) pushed one by one at in_rate, of every `cycle` of which, once
-    matched, `drop` are duplicates; the push that completes a cycle returns the output frames at out_rate its survivors produce, flush()
-    those of the partial last cycle and the inner converter's flush."""
-
-    _destroy = staticmethod(lambda h: lib().fldr_pulldown_destroy(h))
+    matched, `drop` are duplicates; push, flush, reset and last_report are fldr_rate.CycleStream's."""
+    _api, _Report = _API, Report
 
     def __init__(self, native_model, H, W, fmt=None, in_rate=(30000, 1001), out_rate=(60000, 1001), cycle=5, drop=1, anchor=0, post=POST_KEEP,
                  scene=True, scene_params=None, params=None):
         fmt = fmt or Format()
         cfg = make_config(H, W, fmt, in_rate, out_rate, cycle, drop, anchor, post, scene, native_model.device.index or 0, scene_params, params)
-        self._h = ctypes.c_void_p()
-        self.model = native_model                                    # the stream uses the model: keep it alive
-        _check(lib().fldr_pulldown_create(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_pulldown_create")
-        self.H, self.W, self.format, self.cycle, self.drop = int(H), int(W), fmt, int(cycle), int(drop)
-        self.max_out = lib().fldr_pulldown_max_out(self._h)
-        self._stage(fmt, H, W, self.max_out)
-        self.last_report = None
-
-    def _done(self, n, rep):
-        self.last_report = rep.as_dict() if rep.n_frames else None
-        return self._taken(n)
-
-    def push(self, frame):
-        """-> the list of output frames due (tuples of numpy planes, fresh copies): empty unless the push completes a cycle;
-        self.last_report: that cycle's report dict, else None."""
-        fr = frame_struct(frame)
-        n = ctypes.c_int(-1)
-        rep = Report()
-        _check(lib().fldr_pulldown_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n), ctypes.byref(rep)), "fldr_pulldown_push")
-        return self._done(n.value, rep)
-
-    def flush(self):
-        n = ctypes.c_int(-1)
-        rep = Report()
-        _check(lib().fldr_pulldown_flush(self._h, self._out_structs(), ctypes.byref(n), ctypes.byref(rep)), "fldr_pulldown_flush")
-        return self._done(n.value, rep)
-
-    def reset(self):
-        _check(lib().fldr_pulldown_reset(self._h), "fldr_pulldown_reset")
+        self._create(native_model, cfg, H, W, fmt, cycle, drop)

@@ -247,3 +247,104 @@ class Converter(fldr_video.HostStream):
 
     def reset(self):
         _check(lib().fldr_rate_reset(self._h), "fldr_rate_reset")
+
+
+# ---- what the bindings of the libraries above this one share (fldr_cadence, fldr_pulldown, fldr_probe) ------------------------------------
+class Binding:
+    """One library on the rate library: its name (the functions are fldr_<name>_*), path, header version, the signatures of its functions
+    and its struct mirrors -> lib() (loads on first use, after libfldr_rate.so), its error class `Error` (named error_name) and check()."""
+
+    def __init__(self, name, path, version, signatures, structs, error_name):
+        self.name, self.path, self.version, self.signatures, self.structs = name, path, version, signatures, structs
+        self._lib = None
+        api = self
+
+        def init(self, what, code):
+            RuntimeError.__init__(self, "%s failed: %s (code %d)" % (what, api.fn("error_string")(code).decode(), code))
+            self.code = code
+
+        self.Error = type(error_name, (RuntimeError,), {"__init__": init})
+
+    def lib(self):
+        if self._lib is None:
+            lib()
+            self._lib = fldr_model.load_library(self.path, self.signatures, self.structs, "fldr_" + self.name, self.version)
+        return self._lib
+
+    def fn(self, name):
+        return getattr(self.lib(), "fldr_%s_%s" % (self.name, name))
+
+    def check(self, code, what):
+        if code != 0:
+            raise self.Error(what, code)
+
+
+def _ref(x):
+    return ctypes.byref(x) if x is not None else None
+
+
+def state_tensor(n_bytes, device):
+    """A measure state: n_bytes of device memory (torch's allocations are 256-byte aligned)."""
+    return torch.empty(n_bytes, dtype=torch.uint8, device=device)
+
+
+def read_struct(cls, state):
+    """The result struct `cls` at the start of a measure state tensor (synchronising copy) -> its dict, plus "reserved": the spare words."""
+    r = cls.from_buffer_copy(state[:ctypes.sizeof(cls)].cpu().numpy().tobytes())
+    d = r.as_dict()
+    d["reserved"] = [int(v) for v in r.reserved]
+    return d
+
+
+def inner_rate(in_rate, cycle, drop):
+    """The input rate of the inner converter of a cycle stream: in_rate x (cycle - drop) / cycle, a Fraction."""
+    return _rate(in_rate) * (int(cycle) - int(drop)) / int(cycle)
+
+
+def inner_rate_raw(api, Config, in_num, in_den, cycle, drop):
+    """fldr_<name>_inner_rate on a Config with only these four words set -> (code, num, den); does not raise."""
+    cfg = Config()
+    cfg.rate.in_num, cfg.rate.in_den, cfg.cycle, cfg.drop = int(in_num), int(in_den), int(cycle), int(drop)
+    n, d = ctypes.c_int32(0), ctypes.c_int32(0)
+    return api.fn("inner_rate")(ctypes.byref(cfg), ctypes.byref(n), ctypes.byref(d)), n.value, d.value
+
+
+class CycleStream(fldr_video.HostStream):
+    """What Cadence and Pulldown share: frames pushed one by one at in_rate, of every `cycle` of which `drop` are dropped; the push that
+    completes a cycle returns the output frames at out_rate its survivors produce, flush() those of the partial last cycle and the inner
+    converter's flush.  A subclass names its library (`_api`, a Binding) and its report struct (`_Report`) and makes the configuration."""
+
+    def _destroy(self, h):
+        self._api.fn("destroy")(h)
+
+    def _create(self, native_model, cfg, H, W, fmt, cycle, drop):
+        self._h = ctypes.c_void_p()
+        self.model = native_model                                    # the stream uses the model: keep it alive
+        self._api.check(self._api.fn("create")(native_model._h, ctypes.byref(cfg), ctypes.byref(self._h)), "fldr_%s_create" % self._api.name)
+        self.H, self.W, self.format, self.cycle, self.drop = int(H), int(W), fmt, int(cycle), int(drop)
+        self.max_out = self._api.fn("max_out")(self._h)
+        self._stage(fmt, H, W, self.max_out)
+        self.last_report = None
+
+    def _done(self, n, rep):
+        self.last_report = rep.as_dict() if rep.n_frames else None
+        return self._taken(n)
+
+    def push(self, frame):
+        """-> the list of output frames due (tuples of numpy planes, fresh copies): empty unless the push completes a cycle;
+        self.last_report: that cycle's report dict, else None."""
+        fr = frame_struct(frame)
+        n = ctypes.c_int(-1)
+        rep = self._Report()
+        self._api.check(self._api.fn("push")(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n), ctypes.byref(rep)),
+                        "fldr_%s_push" % self._api.name)
+        return self._done(n.value, rep)
+
+    def flush(self):
+        n = ctypes.c_int(-1)
+        rep = self._Report()
+        self._api.check(self._api.fn("flush")(self._h, self._out_structs(), ctypes.byref(n), ctypes.byref(rep)), "fldr_%s_flush" % self._api.name)
+        return self._done(n.value, rep)
+
+    def reset(self):
+        self._api.check(self._api.fn("reset")(self._h), "fldr_%s_reset" % self._api.name)

@@ -1,13 +1,14 @@
 // libfldr_probe.so, host side: validation, fldr_probe_measure, the classifier (fldr_probe_frame_class, fldr_probe_classify: pure host
 // functions) and the probe stream (host frames in, three of them on the device, every frame but the first measured against its two
 // neighbours, the results in a pinned ring, a verdict on demand).  The video API's rules for formats and frames, and the stream / device
-// block / pinned block the object owns, come from ../video/frame_host.h.  The only fldr_* function called is fldr_rate_error_string.
+// block / pinned block the object owns, come from ../video/frame_host.h; the checks a luma tile measure shares with the cadence and
+// pulldown libraries' come from ../rate/tile_measure_host.h, which includes it.  The only fldr_* function called is fldr_rate_error_string.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <new>
 
-#include "../video/frame_host.h"
+#include "../rate/tile_measure_host.h"
 #include "probe_internal.h"
 
 using namespace fldr_probe_impl;
@@ -39,24 +40,8 @@ int resolve_params(const fldr_probe_params* p, fldr_probe_params& r) {
     return 0;
 }
 
-// H a multiple of 4, and rows and columns rounded up to whole tiles inside 32 bits with the tile index in 31
-bool size_ok(int H, int W) {
-    const int64_t T = FLDR_PROBE_TILE;
-    if (H < 4 || (H & 3) || W < 1 || H > 0x7fffffff - T || W > 0x7fffffff - T) return false;
-    return ((int64_t)W + T - 1) / T * (((int64_t)H + T - 1) / T) <= 0x7fffffffll;
-}
-
-// planes, then pitches, of the frames given (null entries are skipped), in order: the video library's codes
-int check_frames(const fldr_video_frame* const* fr, int n, const fldr_video_format& fmt, int W) {
-    const bool words = deep(fmt);
-    for (int f = 0; f < n; ++f) {
-        if (!fr[f]) continue;
-        for (int p = 0; p < planes_of(fmt.layout); ++p)
-            if (!fr[f]->plane[p] || (words && ((uintptr_t)fr[f]->plane[p] & 1))) return FLDR_VIDEO_E_PLANE;
-    }
-    for (int f = 0; f < n; ++f) if (fr[f]) CK(check_frame(*fr[f], fmt, W));
-    return 0;
-}
+// H a multiple of 4 (two whole row pairs per field), and a size the tile reduce takes
+bool size_ok(int H, int W) { return !(H & 3) && tiles_ok(H, W, FLDR_PROBE_TILE); }
 
 int check_measure(int H, int W, const fldr_video_format* fmt, const fldr_video_frame* cur, const fldr_video_frame* prev,
                   const fldr_video_frame* next, const fldr_probe_params* p, void* state, fldr_probe_params& r) {
@@ -65,16 +50,13 @@ int check_measure(int H, int W, const fldr_video_format* fmt, const fldr_video_f
     CK(check_format(*fmt));
     const fldr_video_frame* fr[3] = { cur, prev, next };
     CK(check_frames(fr, 3, *fmt, W));
-    if (!state || ((uintptr_t)state & (ALIGN - 1))) return FLDR_RATE_E_STATE;
-    return 0;
+    return check_state(state, FLDR_RATE_E_STATE);
 }
 
 int enqueue_measure(int H, int W, const fldr_video_format& fmt, const fldr_video_frame* cur, const fldr_video_frame* prev,
                     const fldr_video_frame* next, const fldr_probe_params& r, void* state, hipStream_t s) {
     MeasureCall c;
-    c.cur = cur->plane[0]; c.pitch_cur = cur->pitch[0];
-    c.prev = prev ? prev->plane[0] : nullptr; c.pitch_prev = prev ? prev->pitch[0] : 0;
-    c.next = next ? next->plane[0] : nullptr; c.pitch_next = next ? next->pitch[0] : 0;
+    fill_luma(c, cur, prev, next);
     c.H = H; c.W = W; c.mode = luma_mode(deep(fmt), fmt.layout);
     c.comb_thresh = r.comb_thresh; c.tile_sad_min = r.tile_sad_min; c.frame_tile_sad_min = r.frame_tile_sad_min;
     return probe_measure(c, state, s);
@@ -198,8 +180,7 @@ namespace {
 void forget(fldr_probe* c) { c->n = 0; c->measured = 0; }
 
 int fail(fldr_probe* c, int r) {
-    (void)hipStreamSynchronize(c->sm.stream);
-    (void)hipGetLastError();
+    drain(c->sm);
     forget(c);
     return r;
 }
@@ -315,7 +296,7 @@ extern "C" FLDR_PROBE_API int fldr_probe_result_get(fldr_probe* c, int i, fldr_p
 extern "C" FLDR_PROBE_API int fldr_probe_reset(fldr_probe* c) {
     if (!c) return FLDR_RATE_E_ARG;
     DeviceGuard g(c->sm.device);
-    if (g.ok) { (void)hipStreamSynchronize(c->sm.stream); (void)hipGetLastError(); }   // nothing enqueued may still write the pinned ring
+    if (g.ok) drain(c->sm);
     forget(c);
     return 0;
 }

@@ -3,16 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../rate/luma8_device.h"
+#include "../rate/tile_reduce_device.h"
 #include "fldr_probe.h"
 
 namespace fldr_probe_impl {
-using namespace fldr_luma8;
+using namespace fldr_tile_reduce;
 
 // The measure state (FLDR_PROBE_STATE_BYTES of device memory) in lines of 256 bytes: line 0 is the result the caller reads, lines
-// 1 .. STATE_SLOTS are the kernels' accumulator slots; workgroup b adds to slot 1 + b % STATE_SLOTS.
+// 1 .. SLOTS are the kernels' accumulator slots; workgroup b adds to slot 1 + b % SLOTS (../rate/tile_reduce_device.h).
 constexpr int STATE_SLOT_BYTES = 256;
-constexpr int STATE_SLOTS = 63;
 // A slot: N_SUMS uint64 sums, N_KEYS uint64 keys (max over the tiles of (value << 32) | (0xffffffff - index)), N_COUNTS uint32 counts.
 // Sums and keys 0 .. 5: comb[q][k] at 3 q + k; 6, 7: the field SAD of parity 0, 1.  Sums 8 .. 13: lap[k][p] at 8 + 2 k + p.
 // Counts: field_moving_tiles[0], [1], frame_moving_tiles.

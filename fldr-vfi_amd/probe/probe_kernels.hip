@@ -14,11 +14,10 @@
 // result kernel).
 // A tile's counts are reduced inside its wave (over the lane bits that do not tell its two tiles apart), the three comb counts of one
 // anchor packed ten bits each into one word (a tile's count is at most 512); each lane keeps the sums, the maximum keys and the moving
-// counts of its tiles in registers, and its own share of the order sums, which need no tile; the workgroup combines its waves in LDS,
-// and one lane adds the workgroup's words to memory with integer atomics, to the slot of the workgroup's number (STATE_SLOTS lines of
-// their own) — for each maximum one 64-bit atomicMax on (value << 32) | (0xffffffff - index), which gives the lowest index among equal
-// maxima.  Every word is an integer sum, maximum or count, so the order of the atomics does not show in the result.  The one-wave result
-// kernel combines the slots.  No float anywhere.
+// counts of its tiles in registers, and its own share of the order sums, which need no tile.  What becomes of those words — the keys,
+// the workgroup's slot of the state, the atomics, the grid — is the tile reduce of ../rate/tile_reduce_device.h, here with N_SUMS sums,
+// N_KEYS keys and N_COUNTS counts; the meeting of the waves in LDS and the result kernel's gather, which it describes, are written out
+// below.  No float anywhere.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -26,9 +25,8 @@
 
 namespace fldr_probe_impl {
 
-#define PB_THREADS 256
-#define PB_WAVES (PB_THREADS / 64)
-#define PB_MAX_BLOCKS 2048       // 8 workgroups per CU of an MI355X; larger frames walk with the grid's strides
+#define PB_THREADS THREADS
+#define PB_WAVES WAVES
 #define PB_TILE FLDR_PROBE_TILE
 #define PB_WAVE_BYTES 64         // of a row, per wave
 
@@ -43,32 +41,7 @@ struct ProbeArgs {
     uint8_t* state;
 };
 
-__global__ __launch_bounds__(PB_THREADS) void probe_zero_kernel(uint8_t* state) {
-    uint4* p = reinterpret_cast<uint4*>(state);                                         // 256 x 64 = FLDR_PROBE_STATE_BYTES
-    static_assert(PB_THREADS * 64 == FLDR_PROBE_STATE_BYTES, "four uint4 per thread");
-#pragma unroll
-    for (int i = 0; i < 4; ++i) p[threadIdx.x + i * PB_THREADS] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-// y8 of the 16 bytes at p, each in its sample's low byte, of which `left` (> 0) lie in the row; the others read as 0
-template <int MODE, bool VEC> __device__ __forceinline__ void fetch(const uint8_t* p, int64_t left, uint32_t r[4]) {
-    constexpr int BPS = MODE == Y8_BYTE ? 1 : 2;
-    if (left >= 16) {
-        uint32_t d[4];
-        load16<MODE != Y8_BYTE, VEC>(p, d);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = reduce8<MODE>(d[i]);
-    } else {                                                           // the row's tail: left / BPS samples
-        const int last = (int)left - BPS;                              // a sample past the end reads the row's last one instead, and counts as 0
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = 0u;
-#pragma unroll
-        for (int b = 0; b < 16; b += BPS) {
-            const uint32_t v = (uint32_t)sample8<MODE>(p + (b < last ? b : last));
-            r[b >> 2] |= (b <= last ? v : 0u) << (8 * (b & 3));
-        }
-    }
-}
+__global__ __launch_bounds__(PB_THREADS) void probe_zero_kernel(uint8_t* state) { zero_state<FLDR_PROBE_STATE_BYTES>(state); }
 
 // One row of one group: a and b the lines of cur above and below it, m0 / m1 / m2 the row itself in cur, prev and next.  Returns the
 // three candidates' combed samples, ten bits each, and adds |a + b - 2 m| of each candidate to l0 / l1 / l2.
@@ -93,19 +66,6 @@ template <int MODE> __device__ __forceinline__ uint32_t row16(const uint32_t a[4
         }
     return n0 | (n1 << 10) | (n2 << 20);
 }
-
-// the sum over the lanes of a wave that share a tile: all 64 at depth 10, the 32 with the same bit 1 at depth 8
-template <bool WHOLE> __device__ __forceinline__ uint32_t tile_sum(uint32_t v) {
-    v += (uint32_t)__shfl_xor((int)v, 32, 64);
-    v += (uint32_t)__shfl_xor((int)v, 16, 64);
-    v += (uint32_t)__shfl_xor((int)v, 8, 64);
-    v += (uint32_t)__shfl_xor((int)v, 4, 64);
-    v += (uint32_t)__shfl_xor((int)v, 1, 64);
-    if (WHOLE) v += (uint32_t)__shfl_xor((int)v, 2, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long max64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
 template <int MODE, bool VEC>
 __global__ __launch_bounds__(PB_THREADS) void probe_tiles_kernel(ProbeArgs a) {
@@ -188,7 +148,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_tiles_kernel(ProbeArgs a) {
         }
         const uint32_t tx = col * TPW + (TPW == 2 ? (uint32_t)(group >> 1) : 0u);
         const bool exists = tx < a.tiles_x;                            // the second tile of the last wave column may lie past the frame
-        const unsigned long long low = (unsigned long long)(0xffffffffu - (ty * a.tiles_x + tx));
+        const unsigned long long low = key_low(ty * a.tiles_x + tx);
         uint32_t t[4], v[N_KEYS];
 #pragma unroll
         for (int k = 0; k < 4; ++k) t[k] = tile_sum<TPW == 1>(cnt[k]);    // the tile's counts, in every lane of the tile
@@ -200,7 +160,7 @@ __global__ __launch_bounds__(PB_THREADS) void probe_tiles_kernel(ProbeArgs a) {
 #pragma unroll
         for (int j = 0; j < N_KEYS; ++j) {
             sum[j] += v[j];
-            key[j] = max64(key[j], exists ? ((unsigned long long)v[j] << 32) | low : 0ull);
+            key[j] = max64(key[j], exists ? pack_key(v[j], low) : 0ull);
         }
         count[0] += exists && v[6] >= a.tile_sad_min ? 1u : 0u;
         count[1] += exists && v[7] >= a.tile_sad_min ? 1u : 0u;
@@ -240,23 +200,15 @@ __global__ __launch_bounds__(PB_THREADS) void probe_tiles_kernel(ProbeArgs a) {
 #pragma unroll
             for (int j = 0; j < N_COUNTS; ++j) count[j] += w_count[w][j];
         }
-        // a wave without a tile holds key 0, below every tile's key: the low word of a key is never 0 (tile < 2^31)
-        uint8_t* slot = a.state + STATE_SLOT_BYTES * (1 + (blockIdx.y * gridDim.x + blockIdx.x) % STATE_SLOTS);
-        unsigned long long* ssum = reinterpret_cast<unsigned long long*>(slot + SLOT_SUM_OFFSET);
-        unsigned long long* skey = reinterpret_cast<unsigned long long*>(slot + SLOT_KEY_OFFSET);
-        uint32_t* scount = reinterpret_cast<uint32_t*>(slot + SLOT_COUNT_OFFSET);
-#pragma unroll
-        for (int j = 0; j < N_SUMS; ++j) if (sum[j]) atomicAdd(ssum + j, sum[j]);
-#pragma unroll
-        for (int j = 0; j < N_KEYS; ++j) atomicMax(skey + j, key[j]);
-#pragma unroll
-        for (int j = 0; j < N_COUNTS; ++j) if (count[j]) atomicAdd(scount + j, count[j]);
+        uint8_t* slot = slot_of<STATE_SLOT_BYTES>(a.state);
+        slot_add_all<N_SUMS, N_KEYS, N_COUNTS>(slot_u64(slot, SLOT_SUM_OFFSET), slot_u64(slot, SLOT_KEY_OFFSET),
+                                               reinterpret_cast<uint32_t*>(slot + SLOT_COUNT_OFFSET), sum, key, count);
     }
 }
 
 // one wave: lane l >= 1 takes slot l (line 0 of the state is the result), the wave combines them, lane 0 writes
 __global__ __launch_bounds__(64) void probe_result_kernel(uint8_t* state, int has_prev, int has_next) {
-    static_assert(STATE_SLOTS == 63 && STATE_SLOT_BYTES * (STATE_SLOTS + 1) == FLDR_PROBE_STATE_BYTES, "one slot per lane but lane 0");
+    static_assert(STATE_SLOT_BYTES * (SLOTS + 1) == FLDR_PROBE_STATE_BYTES, "one slot per lane but lane 0");
     const int lane = threadIdx.x;
     const uint8_t* slot = state + STATE_SLOT_BYTES * lane;
     unsigned long long sum[N_SUMS], key[N_KEYS];
@@ -285,14 +237,14 @@ __global__ __launch_bounds__(64) void probe_result_kernel(uint8_t* state, int ha
             const bool given = k == FLDR_PROBE_C || (k == FLDR_PROBE_P ? has_prev : has_next);
             const int j = 3 * q + k;
             r->comb[q][k] = given ? sum[j] : 0ull;
-            r->max_tile_comb[q][k] = given ? (uint32_t)(key[j] >> 32) : 0u;
-            r->max_tile[q][k] = given ? 0xffffffffu - (uint32_t)key[j] : 0u;
+            r->max_tile_comb[q][k] = given ? key_value(key[j]) : 0u;
+            r->max_tile[q][k] = given ? key_index(key[j]) : 0u;
         }
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         r->field_sad[p] = has_prev ? sum[6 + p] : 0ull;
-        r->field_max_tile_sad[p] = has_prev ? (uint32_t)(key[6 + p] >> 32) : 0u;
-        r->field_max_tile[p] = has_prev ? 0xffffffffu - (uint32_t)key[6 + p] : 0u;
+        r->field_max_tile_sad[p] = has_prev ? key_value(key[6 + p]) : 0u;
+        r->field_max_tile[p] = has_prev ? key_index(key[6 + p]) : 0u;
         r->field_moving_tiles[p] = has_prev ? count[p] : 0u;
     }
     r->frame_moving_tiles = has_prev ? count[2] : 0u;
@@ -319,18 +271,15 @@ int probe_measure(const MeasureCall& c, void* state, hipStream_t stream) {
     a.pitch_cur = c.pitch_cur; a.pitch_prev = c.prev ? c.pitch_prev : 0; a.pitch_next = c.next ? c.pitch_next : 0;
     a.row_bytes = luma_row_bytes(c.W, c.mode);
     a.H = c.H;
-    a.tiles_x = (uint32_t)((c.W + PB_TILE - 1) / PB_TILE);
-    a.tiles_y = (uint32_t)((c.H + PB_TILE - 1) / PB_TILE);
+    a.tiles_x = tiles_of(c.W, PB_TILE);
+    a.tiles_y = tiles_of(c.H, PB_TILE);
     a.cols = (uint32_t)((a.row_bytes + PB_WAVE_BYTES - 1) / PB_WAVE_BYTES);
     a.thresh2 = c.comb_thresh * c.comb_thresh;
     a.tile_sad_min = (uint32_t)c.tile_sad_min;
     a.frame_tile_sad_min = (uint32_t)c.frame_tile_sad_min;
     a.state = (uint8_t*)state;
-    // a missing frame decides nothing about the loads: null and pitch 0 are 16-byte aligned
-    const bool vec = luma_vec_ok(c.cur, a.pitch_cur, c.prev, a.pitch_prev) && luma_vec_ok(c.cur, a.pitch_cur, c.next, a.pitch_next);
-    // every workgroup's wave 0 has a column: blockIdx.x * PB_WAVES < cols and blockIdx.y < tiles_y
-    const uint32_t bx = min((a.cols + PB_WAVES - 1) / PB_WAVES, (uint32_t)PB_MAX_BLOCKS);
-    const dim3 blocks(bx, min(a.tiles_y, (uint32_t)PB_MAX_BLOCKS / bx));
+    const bool vec = luma_vec_ok3(c.cur, a.pitch_cur, c.prev, a.pitch_prev, c.next, a.pitch_next);
+    const dim3 blocks = tile_grid(a.cols, a.tiles_y);
     probe_zero_kernel<<<1, PB_THREADS, 0, stream>>>(a.state);
     SAMPLE16_LAUNCH(probe_tiles_kernel, c.mode, vec, blocks, PB_THREADS, stream, a);
     probe_result_kernel<<<1, 64, 0, stream>>>(a.state, c.prev ? 1 : 0, c.next ? 1 : 0);

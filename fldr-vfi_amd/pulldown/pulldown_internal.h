@@ -3,16 +3,15 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../rate/luma8_device.h"
+#include "../rate/tile_reduce_device.h"
 #include "fldr_pulldown.h"
 
 namespace fldr_pulldown_impl {
-using namespace fldr_luma8;
+using namespace fldr_tile_reduce;
 
 // The measure state (FLDR_PULLDOWN_STATE_BYTES of device memory) in lines of 128 bytes: line 0 begins with the result the caller reads,
-// lines 1 .. STATE_SLOTS are the kernels' accumulator slots; workgroup b adds to slot 1 + b % STATE_SLOTS.
+// lines 1 .. SLOTS are the kernels' accumulator slots; workgroup b adds to slot 1 + b % SLOTS (../rate/tile_reduce_device.h).
 constexpr int STATE_SLOT_BYTES = 128;
-constexpr int STATE_SLOTS = 63;
 constexpr int SLOT_COMB_OFFSET = 0;        // uint64 x 3: the combed samples of each candidate in the slot's workgroups
 constexpr int SLOT_KEY_OFFSET = 24;        // uint64 x 3: max over their tiles of (tile_comb << 32) | (0xffffffff - index)
 constexpr int SLOT_DSAD_OFFSET = 48;       // uint64: the sum of the anchor rows' tile sums

@@ -13,11 +13,9 @@
 // The common case — a whole group of an inner pair with all three frames given — issues its six loads together; the general path
 // serves the frame's first and last pair, the row tails and the calls without prev or next.
 // A tile's four counts are reduced inside its wave (over the lane bits that do not tell its two tiles apart); each lane keeps the
-// sums, the maximum keys and the moving count of its tiles in registers, the workgroup combines its waves in LDS, and one lane adds the
-// workgroup's words to memory with integer atomics, to the slot of the workgroup's number (STATE_SLOTS lines of their own) — for each
-// maximum one 64-bit atomicMax on (value << 32) | (0xffffffff - index), which gives the lowest index among equal maxima.  Every word is
-// an integer sum, maximum or count, so the order of the atomics does not show in the result.  The one-wave result kernel combines the
-// slots and takes the decision.  No float anywhere.
+// sums, the maximum keys and the moving count of its tiles in registers.  What becomes of those words — the keys, the workgroup's slot
+// of the state, the atomics, the result kernel's gather, the grid — is the tile reduce of ../rate/tile_reduce_device.h, here with four
+// sums, four keys and one count; the result kernel also takes the decision.  No float anywhere.
 //
 // The assembly is a copy kernel, one launch per plane: a wave takes 1024 bytes of one row, so the choice of the row's source — cur on
 // the anchor rows, S_match on the others, or the line average of cur — is wave-uniform; match and combed come from the arguments or,
@@ -29,9 +27,8 @@
 
 namespace fldr_pulldown_impl {
 
-#define PK_THREADS 256
-#define PK_WAVES (PK_THREADS / 64)
-#define PK_MAX_BLOCKS 2048       // 8 workgroups per CU of an MI355X; larger frames walk with the grid's strides
+#define PK_THREADS THREADS
+#define PK_WAVES WAVES
 #define PK_TILE FLDR_PULLDOWN_TILE
 #define PK_WAVE_BYTES 64         // of a row, per wave
 
@@ -46,31 +43,7 @@ struct MeasureArgs {
     uint8_t* state;
 };
 
-__global__ __launch_bounds__(PK_THREADS) void pulldown_zero_kernel(uint8_t* state) {
-    uint4* p = reinterpret_cast<uint4*>(state);                                         // 256 x 32 = FLDR_PULLDOWN_STATE_BYTES
-    p[threadIdx.x] = make_uint4(0u, 0u, 0u, 0u);
-    p[threadIdx.x + PK_THREADS] = make_uint4(0u, 0u, 0u, 0u);
-}
-
-// y8 of the 16 bytes at p, each in its sample's low byte, of which `left` (> 0) lie in the row; the others read as 0
-template <int MODE, bool VEC> __device__ __forceinline__ void fetch(const uint8_t* p, int64_t left, uint32_t r[4]) {
-    constexpr int BPS = MODE == Y8_BYTE ? 1 : 2;
-    if (left >= 16) {
-        uint32_t d[4];
-        load16<MODE != Y8_BYTE, VEC>(p, d);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = reduce8<MODE>(d[i]);
-    } else {                                                           // the row's tail: left / BPS samples
-        const int last = (int)left - BPS;                              // a sample past the end reads the row's last one instead, and counts as 0
-#pragma unroll
-        for (int i = 0; i < 4; ++i) r[i] = 0u;
-#pragma unroll
-        for (int b = 0; b < 16; b += BPS) {
-            const uint32_t v = (uint32_t)sample8<MODE>(p + (b < last ? b : last));
-            r[b >> 2] |= (b <= last ? v : 0u) << (8 * (b & 3));
-        }
-    }
-}
+__global__ __launch_bounds__(PK_THREADS) void pulldown_zero_kernel(uint8_t* state) { zero_state<FLDR_PULLDOWN_STATE_BYTES>(state); }
 
 // the samples of m that lie outside the span of a and b by more than the threshold on both sides
 template <int MODE> __device__ __forceinline__ uint32_t combed16(const uint32_t a[4], const uint32_t b[4], const uint32_t m[4], int thresh2) {
@@ -85,19 +58,6 @@ template <int MODE> __device__ __forceinline__ uint32_t combed16(const uint32_t 
         }
     return n;
 }
-
-// the sum over the lanes of a wave that share a tile: all 64 at depth 10, the 32 with the same bit 1 at depth 8
-template <bool WHOLE> __device__ __forceinline__ uint32_t tile_sum(uint32_t v) {
-    v += (uint32_t)__shfl_xor((int)v, 32, 64);
-    v += (uint32_t)__shfl_xor((int)v, 16, 64);
-    v += (uint32_t)__shfl_xor((int)v, 8, 64);
-    v += (uint32_t)__shfl_xor((int)v, 4, 64);
-    v += (uint32_t)__shfl_xor((int)v, 1, 64);
-    if (WHOLE) v += (uint32_t)__shfl_xor((int)v, 2, 64);
-    return v;
-}
-
-__device__ __forceinline__ unsigned long long max64(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
 
 template <int MODE, bool VEC>
 __global__ __launch_bounds__(PK_THREADS) void pulldown_tiles_kernel(MeasureArgs a) {
@@ -162,12 +122,12 @@ __global__ __launch_bounds__(PK_THREADS) void pulldown_tiles_kernel(MeasureArgs 
         }
         const uint32_t tx = col * TPW + (TPW == 2 ? (uint32_t)(group >> 1) : 0u);
         const bool exists = tx < a.tiles_x;                            // the second tile of the last wave column may lie past the frame
-        const unsigned long long low = (unsigned long long)(0xffffffffu - (ty * a.tiles_x + tx));
+        const unsigned long long low = key_low(ty * a.tiles_x + tx);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const uint32_t t = tile_sum<TPW == 1>(cnt[k]);             // the tile's count, in every lane of the tile
             sum[k] += t;
-            key[k] = max64(key[k], exists ? ((unsigned long long)t << 32) | low : 0ull);
+            key[k] = max64(key[k], exists ? pack_key(t, low) : 0ull);
             if (k == 3) moving += exists && t >= a.tile_sad_min ? 1u : 0u;
         }
     }
@@ -192,62 +152,50 @@ __global__ __launch_bounds__(PK_THREADS) void pulldown_tiles_kernel(MeasureArgs 
             for (int k = 0; k < 4; ++k) { sum[k] += w_sum[w][k]; key[k] = max64(key[k], w_key[w][k]); }
             moving += w_moving[w];
         }
-        // a wave without a tile holds key 0, below every tile's key: the low word of a key is never 0 (tile < 2^31)
-        uint8_t* slot = a.state + STATE_SLOT_BYTES * (1 + (blockIdx.y * gridDim.x + blockIdx.x) % STATE_SLOTS);
-        unsigned long long* comb = reinterpret_cast<unsigned long long*>(slot + SLOT_COMB_OFFSET);
-        unsigned long long* ckey = reinterpret_cast<unsigned long long*>(slot + SLOT_KEY_OFFSET);
+        // the words of a slot lie candidate by candidate, then the anchor rows': they are sent in that order
+        uint8_t* slot = slot_of<STATE_SLOT_BYTES>(a.state);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
-            if (sum[k]) atomicAdd(comb + k, sum[k]);
-            atomicMax(ckey + k, key[k]);
+            slot_add(slot_u64(slot, SLOT_COMB_OFFSET) + k, sum[k]);
+            slot_max(slot_u64(slot, SLOT_KEY_OFFSET) + k, key[k]);
         }
-        if (sum[3]) atomicAdd(reinterpret_cast<unsigned long long*>(slot + SLOT_DSAD_OFFSET), sum[3]);
-        atomicMax(reinterpret_cast<unsigned long long*>(slot + SLOT_DKEY_OFFSET), key[3]);
-        if (moving) atomicAdd(reinterpret_cast<uint32_t*>(slot + SLOT_DMOVING_OFFSET), moving);
+        slot_add(slot_u64(slot, SLOT_DSAD_OFFSET), sum[3]);
+        slot_max(slot_u64(slot, SLOT_DKEY_OFFSET), key[3]);
+        slot_add(reinterpret_cast<uint32_t*>(slot + SLOT_DMOVING_OFFSET), moving);
     }
 }
 
 // one wave: lane l >= 1 takes slot l (line 0 of the state is the result), the wave combines them, lane 0 decides and writes
 __global__ __launch_bounds__(64) void pulldown_result_kernel(uint8_t* state, int allowed, uint32_t comb_tile_min, int has_prev) {
-    static_assert(STATE_SLOTS == 63 && STATE_SLOT_BYTES * (STATE_SLOTS + 1) == FLDR_PULLDOWN_STATE_BYTES, "one slot per lane but lane 0");
+    static_assert(STATE_SLOT_BYTES * (SLOTS + 1) == FLDR_PULLDOWN_STATE_BYTES, "one slot per lane but lane 0");
     const int lane = threadIdx.x;
     const uint8_t* slot = state + STATE_SLOT_BYTES * lane;
     unsigned long long sum[4], key[4];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        sum[k] = lane ? reinterpret_cast<const unsigned long long*>(slot + SLOT_COMB_OFFSET)[k] : 0ull;
-        key[k] = lane ? reinterpret_cast<const unsigned long long*>(slot + SLOT_KEY_OFFSET)[k] : 0ull;
-    }
-    sum[3] = lane ? *reinterpret_cast<const unsigned long long*>(slot + SLOT_DSAD_OFFSET) : 0ull;
-    key[3] = lane ? *reinterpret_cast<const unsigned long long*>(slot + SLOT_DKEY_OFFSET) : 0ull;
-    uint32_t moving = lane ? *reinterpret_cast<const uint32_t*>(slot + SLOT_DMOVING_OFFSET) : 0u;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            sum[k] += __shfl_xor(sum[k], m, 64);
-            key[k] = max64(key[k], __shfl_xor(key[k], m, 64));
-        }
-        moving += (uint32_t)__shfl_xor((int)moving, m, 64);
-    }
+    uint32_t moving;
+    slot_load<unsigned long long, 3>(slot + SLOT_COMB_OFFSET, lane, sum);
+    slot_load<unsigned long long, 3>(slot + SLOT_KEY_OFFSET, lane, key);
+    slot_load<unsigned long long, 1>(slot + SLOT_DSAD_OFFSET, lane, sum + 3);
+    slot_load<unsigned long long, 1>(slot + SLOT_DKEY_OFFSET, lane, key + 3);
+    slot_load<uint32_t, 1>(slot + SLOT_DMOVING_OFFSET, lane, &moving);
+    wave_combine<4, 4, 1>(sum, key, &moving);
     if (lane != 0) return;
     fldr_pulldown_result* r = reinterpret_cast<fldr_pulldown_result*>(state);
     int match = -1;
     unsigned long long best_tile = 0, best_sum = 0;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-        const unsigned long long tile = key[k] >> 32;
+        const unsigned long long tile = key_value(key[k]);
         r->comb[k] = sum[k];
         r->max_tile_comb[k] = (uint32_t)tile;
-        r->max_tile[k] = 0xffffffffu - (uint32_t)key[k];
+        r->max_tile[k] = key_index(key[k]);
         if (!(allowed >> k & 1)) continue;
         if (match < 0 || tile < best_tile || (tile == best_tile && sum[k] < best_sum)) { match = k; best_tile = tile; best_sum = sum[k]; }   // strict: ties stay with the earlier candidate
     }
     r->match = match;
     r->combed = best_tile >= comb_tile_min ? 1u : 0u;
     r->dup_sad = sum[3];
-    r->dup_max_tile_sad = (uint32_t)(key[3] >> 32);
-    r->dup_max_tile = has_prev ? 0xffffffffu - (uint32_t)key[3] : 0u;
+    r->dup_max_tile_sad = key_value(key[3]);
+    r->dup_max_tile = has_prev ? key_index(key[3]) : 0u;
     r->dup_moving_tiles = moving;
 #pragma unroll
     for (int i = 0; i < 5; ++i) r->reserved[i] = 0u;
@@ -259,17 +207,14 @@ int pulldown_measure(const MeasureCall& c, void* state, hipStream_t stream) {
     a.pitch_cur = c.pitch_cur; a.pitch_prev = c.prev ? c.pitch_prev : 0; a.pitch_next = c.next ? c.pitch_next : 0;
     a.row_bytes = luma_row_bytes(c.W, c.mode);
     a.H = c.H; a.q = c.anchor;
-    a.tiles_x = (uint32_t)((c.W + PK_TILE - 1) / PK_TILE);
-    a.tiles_y = (uint32_t)((c.H + PK_TILE - 1) / PK_TILE);
+    a.tiles_x = tiles_of(c.W, PK_TILE);
+    a.tiles_y = tiles_of(c.H, PK_TILE);
     a.cols = (uint32_t)((a.row_bytes + PK_WAVE_BYTES - 1) / PK_WAVE_BYTES);
     a.thresh2 = c.comb_thresh * c.comb_thresh;
     a.tile_sad_min = (uint32_t)c.tile_sad_min;
     a.state = (uint8_t*)state;
-    // a missing frame decides nothing about the loads: null and pitch 0 are 16-byte aligned
-    const bool vec = luma_vec_ok(c.cur, a.pitch_cur, c.prev, a.pitch_prev) && luma_vec_ok(c.cur, a.pitch_cur, c.next, a.pitch_next);
-    // every workgroup's wave 0 has a column: blockIdx.x * PK_WAVES < cols and blockIdx.y < tiles_y
-    const uint32_t bx = min((a.cols + PK_WAVES - 1) / PK_WAVES, (uint32_t)PK_MAX_BLOCKS);
-    const dim3 blocks(bx, min(a.tiles_y, (uint32_t)PK_MAX_BLOCKS / bx));
+    const bool vec = luma_vec_ok3(c.cur, a.pitch_cur, c.prev, a.pitch_prev, c.next, a.pitch_next);
+    const dim3 blocks = tile_grid(a.cols, a.tiles_y);
     pulldown_zero_kernel<<<1, PK_THREADS, 0, stream>>>(a.state);
     SAMPLE16_LAUNCH(pulldown_tiles_kernel, c.mode, vec, blocks, PK_THREADS, stream, a);
     pulldown_result_kernel<<<1, 64, 0, stream>>>(a.state, c.allowed, (uint32_t)c.comb_tile_min, c.prev ? 1 : 0);

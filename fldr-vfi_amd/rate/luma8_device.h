@@ -1,8 +1,8 @@
 // The 8-bit luma reader of the measure kernels (fldr_rate.h's y8): how the value sits in a sample of each format, the reduced samples of a
 // dword, their sum of absolute differences, and the host's side of it (the mode of a format, the bytes of a row, whether the 16-byte loads
 // may be used).  The 16 bytes of a row as four dwords (load16) and the launch of a kernel template by mode (SAMPLE16_LAUNCH) are those of
-// ../video/sample16_device.h.  Included through rate_internal.h and ../cadence/cadence_internal.h: scene_accumulate_kernel and
-// repeat_tiles_kernel read luma with the same text, inlined into each.
+// ../video/sample16_device.h.  Included through rate_internal.h and, by way of tile_reduce_device.h, the cadence, pulldown and probe
+// libraries' internal headers: scene_accumulate_kernel and the three tiles kernels read luma with the same text, inlined into each.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

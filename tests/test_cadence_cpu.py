@@ -274,6 +274,46 @@ def test_stream_argument_errors_before_any_device_call():
     l.fldr_cadence_destroy(None)
 
 
+@pytest.mark.parametrize("layout,depth", [("nv12", 8), ("i420", 10)])
+def test_two_faults_at_once_answer_in_the_recorded_order(layout, depth):
+    """The checks of a measure and of a create sit in headers this library shares with the pulldown and probe libraries
+    (rate/tile_measure_host.h, rate/cycle_stream_host.h): which of two simultaneous faults is reported is decided there.  Every code
+    here was recorded from the library as it was before that text was shared."""
+    import fldr_cadence as K
+    import fldr_rate as R
+    import fldr_video as V
+    H = W = 64
+    _, base, fr = _frames(V, layout, depth)
+    fmt, bad_fmt = V.Format(layout, depth=depth), V.Format(layout, depth=depth)
+    bad_fmt.layout = 2
+    assert K.repeat_measure_raw(H, W, fmt, fr, K.RepeatParams(-1), base + 16, None) == K.E_ARG         # a bad threshold and a misaligned state
+    assert K.repeat_measure_raw(0, W, fmt, fr, None, None, None) == K.E_ARG                           # a bad size and no state
+    assert K.repeat_measure_raw(H, W, bad_fmt, fr, None, base + 16, None) == V.E_FORMAT
+    # the two frames are checked one after the other, each planes first: a short pitch in I0 comes before a missing plane in I1 ...
+    _, base, fr = _frames(V, layout, depth)
+    fr[0].pitch[0], fr[1].plane[0] = 2, None
+    assert K.repeat_measure_raw(H, W, fmt, fr, None, base, None) == V.E_PITCH
+    # ... and a missing chroma plane in I0 before a short luma pitch in I1
+    _, base, fr = _frames(V, layout, depth)
+    fr[0].plane[1], fr[1].pitch[0] = None, 2
+    assert K.repeat_measure_raw(H, W, fmt, fr, None, base, None) == V.E_PLANE
+    _, base, fr = _frames(V, layout, depth)
+    fr[1].pitch[0] = 2
+    assert K.repeat_measure_raw(H, W, fmt, fr, None, base + 16, None) == V.E_PITCH
+    # the stream: fldr_rate_create's checks, then cycle, drop, the threshold and the reserved words, then the derived ratio
+    l, h = K.lib(), ctypes.c_void_p()
+    create = lambda **kw: _create(l, h, **kw)
+    many = dict(in_num=30, in_den=1, out_num=24 * 65 * 4, out_den=1)        # the derived rate has too many outputs per frame
+    big = dict(in_num=2 ** 31 - 1, in_den=1, out_num=2 ** 31 - 1, out_den=1)   # a derived term outside int32
+    assert create(**many) == R.E_RATIO and create(**big) == R.E_RATIO          # alone
+    assert create(cycle=0, in_num=0) == R.E_RATIO and create(cycle=17, H=1) == R.E_ARG
+    assert create(cycle=0, **many) == K.E_ARG and create(drop=5, **big) == K.E_ARG
+    assert create(mutate=lambda c: c.reserved.__setitem__(1, 1), **many) == K.E_ARG
+    assert create(mutate=lambda c: setattr(c.repeat, "tile_sad_min", -1), **many) == K.E_ARG
+    assert K.inner_rate_raw(0, 1, 0, 0)[0] == K.E_ARG and K.inner_rate_raw(30, 0, 5, 5)[0] == K.E_ARG
+    assert K.inner_rate_raw(2 ** 31 - 1, 1, 17, 1)[0] == K.E_ARG
+
+
 @pytest.mark.parametrize("in_rate,cycle,drop,want", [(60, 5, 3, Fraction(24)), ((60000, 1001), 5, 3, Fraction(24000, 1001)), (30, 5, 1, Fraction(24)),
                                                       (50, 2, 1, Fraction(25)), (24, 1, 0, Fraction(24)), ((30000, 1001), 16, 15, Fraction(1875, 1001))])
 def test_the_derived_inner_rate(in_rate, cycle, drop, want):

@@ -307,6 +307,40 @@ def test_classify_and_stream_argument_errors_before_any_device_call():
     l.fldr_probe_destroy(None)
 
 
+@pytest.mark.parametrize("layout,depth", [("nv12", 8), ("i420", 10)])
+def test_two_faults_at_once_answer_in_the_recorded_order(layout, depth):
+    """The checks of a measure sit in a header this library shares with the cadence and pulldown libraries (rate/tile_measure_host.h):
+    which of two simultaneous faults is reported is decided there.  Every code here was recorded from the library as it was before
+    that text was shared."""
+    import fldr_probe as K
+    import fldr_video as V
+    b = 2 if depth == 10 else 1
+    buf, base, fr = _host(V, layout, depth)
+    state = base + 3 * H0 * W0 * 2 * b
+    fmt, bad_fmt = V.Format(layout, depth=depth), V.Format(layout, depth=depth)
+    bad_fmt.layout = 2
+    assert K.measure_raw(H0, W0, fmt, fr[0], fr[1], fr[2], K.Params(comb_thresh=-1), state + 16, None) == K.E_ARG   # a bad parameter and a misaligned state
+    assert K.measure_raw(6, W0, fmt, fr[0], fr[1], fr[2], None, None, None) == K.E_ARG                              # a bad size and no state
+    assert K.measure_raw(H0, W0, bad_fmt, fr[0], fr[1], fr[2], None, state + 16, None) == V.E_FORMAT
+    fr[1].pitch[0] = 2
+    assert K.measure_raw(H0, W0, fmt, fr[0], fr[1], fr[2], None, state + 16, None) == V.E_PITCH
+    _, _, fr = _host(V, layout, depth)
+    fr[0].pitch[1], fr[1].plane[1] = 2, None                                 # every plane of every frame before any pitch
+    assert K.measure_raw(H0, W0, fmt, fr[0], fr[1], fr[2], None, state, None) == V.E_PLANE
+    # the stream: size, window, parameters and reserved words all come before the format
+    l, h = K.lib(), ctypes.c_void_p()
+
+    def create(mutate):
+        cfg = K.make_config(64, 64, V.Format("i420"), 8, 2 ** 20)
+        cfg.format.layout = 3
+        mutate(cfg)
+        return l.fldr_probe_create(ctypes.byref(cfg), ctypes.byref(h))
+    assert create(lambda c: None) == V.E_FORMAT
+    assert create(lambda c: setattr(c, "H", 6)) == K.E_ARG and create(lambda c: setattr(c.params, "min_moved", 65)) == K.E_ARG
+    assert create(lambda c: c.reserved.__setitem__(0, 1)) == K.E_ARG
+    assert not buf.any() and not h.value
+
+
 # ---- the oracle against its siblings and on hand-worked frames ------------------------------------------------------------------------------
 @functools.lru_cache(maxsize=None)
 def _measures(name, layout, depth):

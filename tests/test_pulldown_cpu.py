@@ -363,6 +363,45 @@ def test_stream_argument_errors_before_any_device_call():
     l.fldr_pulldown_destroy(None)
 
 
+@pytest.mark.parametrize("layout,depth", [("nv12", 8), ("i420", 10)])
+def test_two_faults_at_once_answer_in_the_recorded_order(layout, depth):
+    """The checks of a measure and of a create sit in headers this library shares with the cadence and probe libraries
+    (rate/tile_measure_host.h, rate/cycle_stream_host.h): which of two simultaneous faults is reported is decided there.  Every code
+    here was recorded from the library as it was before that text was shared."""
+    import fldr_pulldown as K
+    import fldr_rate as R
+    import fldr_video as V
+    b = 2 if depth == 10 else 1
+    buf, base, fr = _host(V, layout, depth)
+    state = base + 4 * H0 * W0 * 2 * b
+    fmt, bad_fmt = V.Format(layout, depth=depth), V.Format(layout, depth=depth)
+    bad_fmt.layout = 2
+    assert K.measure_raw(H0, W0, fmt, fr[0], fr[1], fr[2], 0, K.Params(comb_thresh=-1), state + 16, None) == K.E_ARG   # a bad parameter and a misaligned state
+    assert K.measure_raw(H0, W0, fmt, fr[0], fr[1], fr[2], 2, None, None, None) == K.E_ARG                             # a bad anchor and no state
+    assert K.measure_raw(H0, W0, bad_fmt, fr[0], None, fr[2], 0, None, state, None) == K.E_ARG                         # a frame `allowed` needs, and a bad format
+    assert K.measure_raw(H0, W0, bad_fmt, fr[0], fr[1], fr[2], 0, None, state + 16, None) == V.E_FORMAT
+    fr[1].pitch[0] = 2
+    assert K.measure_raw(H0, W0, fmt, fr[0], fr[1], fr[2], 0, None, state + 16, None) == V.E_PITCH
+    _, _, fr = _host(V, layout, depth)
+    fr[0].pitch[1], fr[1].plane[1] = 2, None                                 # every plane of every frame before any pitch
+    assert K.measure_raw(H0, W0, fmt, fr[0], fr[1], fr[2], 0, None, state, None) == V.E_PLANE
+    _, _, fr = _host(V, layout, depth)
+    fr[3].plane[0], fr[3].pitch[1] = fr[0].plane[0], 1                       # out on cur, and a short pitch in out: the frames before the overlap
+    assert K.assemble_raw(H0, W0, fmt, fr[0], fr[1], fr[2], fr[3], 0, 0, 0, None, 0, None) == V.E_PITCH
+    # the stream: fldr_rate_create's checks, then this library's, then the derived ratio
+    l, h = K.lib(), ctypes.c_void_p()
+    create = lambda **kw: _create(l, h, **kw)
+    many = dict(in_num=30, in_den=1, out_num=24 * 65 * 4, out_den=1)        # the derived rate has too many outputs per frame
+    big = dict(in_num=2 ** 31 - 1, in_den=1, out_num=2 ** 31 - 1, out_den=1)   # a derived term outside int32
+    assert create(**many) == R.E_RATIO and create(**big) == R.E_RATIO          # alone
+    assert create(cycle=0, in_num=0) == R.E_RATIO and create(H=66, in_num=0) == R.E_RATIO and create(cycle=17, H=1) == R.E_ARG
+    assert create(cycle=0, **many) == K.E_ARG and create(drop=5, **big) == K.E_ARG
+    assert create(mutate=lambda c: c.reserved.__setitem__(1, 1), **many) == K.E_ARG
+    assert create(mutate=lambda c: setattr(c.params, "allowed", 8), **many) == K.E_ARG
+    assert K.inner_rate_raw(0, 1, 0, 0)[0] == K.E_ARG and K.inner_rate_raw(30, 0, 5, 5)[0] == K.E_ARG
+    assert K.inner_rate_raw(2 ** 31 - 1, 1, 17, 1)[0] == K.E_ARG
+
+
 @pytest.mark.parametrize("in_rate,cycle,drop,want", [((30000, 1001), 5, 1, Fraction(24000, 1001)), (30, 5, 1, Fraction(24)), (25, 1, 0, Fraction(25)),
                                                       (60, 5, 3, Fraction(24)), ((30000, 1001), 16, 15, Fraction(1875, 1001))])
 def test_the_derived_inner_rate(in_rate, cycle, drop, want):
