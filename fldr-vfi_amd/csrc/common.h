@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <atomic>
+#include <mutex>
 #include "fldr_hip.h"
 
 // Tuning / cross-check hooks (fldr_debug_*, include/fldr_hip_test_hooks.h) and the retired kernel generations that only serve as
@@ -22,18 +23,24 @@
 static inline hipStream_t fldr_s(fldr_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 static inline int fldr_cdiv(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
-// hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device only: remember it per (kernel
-// instantiation, device ordinal) — `done` is one function-local static bit mask per instantiation — so that a process
-// driving several GPUs raises the limit on each of them.  Returns 0 or the hipError_t.
-static inline int fldr_set_max_lds(const void* fn, int bytes, std::atomic<uint64_t>& done) {
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) applies to the CURRENT device only: remember per (kernel instantiation, device
+// ordinal) the LARGEST size set so far — `lim` is one function-local static per instantiation — so that a process driving several
+// GPUs raises the limit on each of them, a launcher whose LDS size depends on the layer (the stride-2 kernels: enc2 runs before the
+// wider enc3) raises it again when a call needs more, and a fixed-size launcher makes exactly one attribute call per device.  The
+// attribute call and the store that publishes it are serialised: a thread that reads `set >= bytes` launches under a limit that is
+// at least that.  Returns 0 or the hipError_t.
+struct FldrLdsLimit { std::atomic<int> set[64]; std::mutex mu; };
+static inline int fldr_set_max_lds(const void* fn, int bytes, FldrLdsLimit& lim) {
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return (int)e;
-    const uint64_t bit = 1ull << (dev & 63);
-    if (done.load(std::memory_order_acquire) & bit) return 0;
+    std::atomic<int>& set = lim.set[dev & 63];
+    if (set.load(std::memory_order_acquire) >= bytes) return 0;
+    std::lock_guard<std::mutex> lk(lim.mu);
+    if (set.load(std::memory_order_acquire) >= bytes) return 0;
     e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) return (int)e;
-    done.fetch_or(bit, std::memory_order_release);
+    set.store(bytes, std::memory_order_release);
     return 0;
 }
 

@@ -419,7 +419,7 @@ static int conv_launch(const ConvArgs& a, int N, hipStream_t s) {
     b.tiles_x = fldr_cdiv(a.Wout, Cfg::TW);
     const int tiles_y = fldr_cdiv(a.Hout, Cfg::TH);
     const size_t lds = sizeof(float) * Cfg::LDS_FLOATS;
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (lds > 64 * 1024)
         if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv_mfma_kernel<KS, STRIDE, MT, NMT, PT, CC>), (int)lds, attr_done)) return e;
     hipLaunchKernelGGL((conv_mfma_kernel<KS, STRIDE, MT, NMT, PT, CC>), dim3(b.tiles_x * tiles_y * b.groups, N), dim3(256), lds, s, b);

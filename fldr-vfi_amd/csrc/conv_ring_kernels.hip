@@ -1305,9 +1305,7 @@ __global__ void ringrow_prepack_kernel(const float* __restrict__ w, const float*
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int c = c32 * 32 + (lane >> 4) * 8 + j;
-        const float x = (co < cout && c < cin) ? w[((int64_t)co * cin + c) * 9 + dy * 3 + dx] * scale : 0.0f;
-        const _Float16 h = (_Float16)x;
-        v[j] = kind == 0 ? h : (_Float16)(x - (float)h);
+        v[j] = fldr_pack_half((co < cout && c < cin) ? w[((int64_t)co * cin + c) * 9 + dy * 3 + dx] * scale : 0.0f, kind);
     }
     reinterpret_cast<h8*>(dst)[i] = v;
 }
@@ -1327,7 +1325,7 @@ FLDR_HOOK int fldr_debug_ringrow_prepack(const float* weight, const float* wpack
 template <int NMT>
 static int ringrow_launch(SpkArgs& a, const float* wrow, int N, int wgs_per_xcd_max, hipStream_t s) {
     using Cfg = RingRowCfg<NMT>;
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv3x3_ringrow_kernel<NMT>), Cfg::LDS_BYTES, attr_done)) return e;
     a.groups = a.cout / (16 * NMT);
     if (int e = spk_fill_geometry(a, N, wgs_per_xcd_max, SPK_TW)) return e;
@@ -1349,7 +1347,7 @@ FLDR_HOOK int fldr_debug_ring_consumers(int v) { if (v == 4 || v == 8) g_ring_co
 template <int NMT, int TERMS, bool HAS_RES, int NC, int TW, bool RW = false>
 static int ring_launch3(SpkArgs& a, int N, int wgs_per_xcd_max, hipStream_t s, int walk_h) {
     using Cfg = RingCfg<NMT, TW, RW>;
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv3x3_ring_kernel<NMT, TERMS, HAS_RES, NC, TW, false, RW>), Cfg::LDS_BYTES, attr_done)) return e;
     if (int e = spk_fill_geometry(a, N, wgs_per_xcd_max, TW, walk_h)) return e;
     a.spin_limit = g_ring_spin_limit;
@@ -1427,7 +1425,7 @@ static int ring_launch(SpkArgs& a, int N, int wpx, hipStream_t s, int walk_h) {
 static int g_ring32 = RING32_DEFAULT;
 FLDR_HOOK int fldr_debug_ring32(int v) { if (v >= 0 && v <= 2) g_ring32 = v; return g_ring32; }
 static int ring32_launch(SpkArgs& a, int N, int wgs_per_xcd_max, hipStream_t s, int walk_h) {
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv3x3_ring32_kernel), Ring32Cfg::LDS_BYTES, attr_done)) return e;
     a.groups = a.cout / 32;
     if (int e = spk_fill_geometry(a, N, wgs_per_xcd_max, SPK_TW, walk_h)) return e;
@@ -1459,21 +1457,14 @@ int fldr_spk_ring_dispatch(SpkArgs& a, int N, int nmt, int terms, int wgs_per_xc
     if (g_ring32 && terms == 3 && nmt >= 2 && a.w32_off && a.cout_store == a.cout && !a.residual && !a.out_f32 && a.out_spk && g_ring_consumers == 8 &&
         g_ring_tile_width == 0 && ring32_pays(a, N, wgs_per_xcd_max, walk_h))
         return ring32_launch(a, N, wgs_per_xcd_max, s, walk_h);
-    if (terms == 1) {
-        if (nmt == 1) return ring_launch<1, 1>(a, N, wgs_per_xcd_max, s, walk_h);
-        if (nmt == 2) return ring_launch<2, 1>(a, N, wgs_per_xcd_max, s, walk_h);
-        return ring_launch<3, 1>(a, N, wgs_per_xcd_max, s, walk_h);
-    }
-    if (nmt == 1) return ring_launch<1, 3>(a, N, wgs_per_xcd_max, s, walk_h);
-    if (nmt == 2) return ring_launch<2, 3>(a, N, wgs_per_xcd_max, s, walk_h);
-    return ring_launch<3, 3>(a, N, wgs_per_xcd_max, s, walk_h);
+    return fldr_dispatch_nmt_terms(nmt, terms, [&](auto NMT, auto TERMS) { return ring_launch<NMT(), TERMS()>(a, N, wgs_per_xcd_max, s, walk_h); });
 }
 
 // Multi-level launch: 8 x 32 tiles, 8 consumer waves; the unit geometry of spk_fill_geometry with the units of all levels.
 template <int NMT, int TERMS, bool HAS_RES>
 static int ring_launch_levels(SpkArgs& a, int n_units, int wgs_per_xcd_max, hipStream_t s) {
     using Cfg = RingCfg<NMT, 32>;
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv3x3_ring_kernel<NMT, TERMS, HAS_RES, 8, 32, true>), Cfg::LDS_BYTES, attr_done)) return e;
     a.tiles_x = 1; a.n_tiles = 1; a.m_tiles = 0; a.m_tiles_x = 0;           // (per level: a.lv)
     a.n_units = n_units;
@@ -1488,8 +1479,7 @@ static int ring_launch_levels(SpkArgs& a, int n_units, int wgs_per_xcd_max, hipS
 }
 
 int fldr_spk_ring_dispatch_levels(SpkArgs& a, int n_units, int nmt, int terms, int wgs_per_xcd_max, hipStream_t s) {
-#define RING_LV(NMT_, T_) (a.residual ? ring_launch_levels<NMT_, T_, true>(a, n_units, wgs_per_xcd_max, s) : ring_launch_levels<NMT_, T_, false>(a, n_units, wgs_per_xcd_max, s))
-    if (terms == 1) return nmt == 1 ? RING_LV(1, 1) : (nmt == 2 ? RING_LV(2, 1) : RING_LV(3, 1));
-    return nmt == 1 ? RING_LV(1, 3) : (nmt == 2 ? RING_LV(2, 3) : RING_LV(3, 3));
-#undef RING_LV
+    return fldr_dispatch_nmt_terms(nmt, terms, [&](auto NMT, auto TERMS) {
+        return a.residual ? ring_launch_levels<NMT(), TERMS(), true>(a, n_units, wgs_per_xcd_max, s) : ring_launch_levels<NMT(), TERMS(), false>(a, n_units, wgs_per_xcd_max, s);
+    });
 }

@@ -15,7 +15,7 @@
 //   32x32x16 (cout <= 64): lane group g = lane / 32 -> row pair g of the step's channel:                    4 steps per chunk
 // k slot j of a lane: dword j / 2 in the order (even x, even x+1, odd x, odd x+1) = kernel column dx {1, 3, 0, 2}... see
 // s2_tap() — the weight prepack uses the same function, so any consistent order works.
-#include "common.h"
+#include "weight_pack.h"
 #include <type_traits>
 #include "row_plan.h"
 
@@ -1234,25 +1234,6 @@ static inline void s2_geometry(int cout, int& mt, int& nmt) {
     else { mt = 32; nmt = 2; }
 }
 
-__global__ void s2_absmax_kernel(const float* __restrict__ w, int64_t n, float* __restrict__ hdr) {
-    __shared__ float red[256];
-    float m = 0.0f;
-    for (int64_t i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(w[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x < S2_HDR) {
-        const float mx = red[0];
-        float scale = 1.0f;
-        if (mx > 0.0f) scale = exp2f(floorf(log2f(8192.0f / mx)));
-        const float v[S2_HDR] = {1.0f / scale, scale, mx, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        hdr[threadIdx.x] = v[threadIdx.x];
-    }
-}
-
 __global__ void s2_prepack_kernel(const float* __restrict__ w, float* __restrict__ wp, int cout, int cin, int mt, int nmt,
                                   int64_t total_h8) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one 8-half element per thread
@@ -1273,9 +1254,7 @@ __global__ void s2_prepack_kernel(const float* __restrict__ w, float* __restrict
     for (int j = 0; j < 8; ++j) {
         int dy, dx;
         s2_tap(rp, j, dy, dx);
-        const float x = (co < cout && c < cin) ? w[(((int64_t)co * cin + c) * 4 + dy) * 4 + dx] * scale : 0.0f;
-        const _Float16 h = (_Float16)x;
-        v[j] = kind == 0 ? h : (_Float16)(x - (float)h);
+        v[j] = fldr_pack_half((co < cout && c < cin) ? w[(((int64_t)co * cin + c) * 4 + dy) * 4 + dx] * scale : 0.0f, kind);
     }
     reinterpret_cast<s2_h8*>(wp + S2_HDR)[i] = v;
 }
@@ -1293,9 +1272,7 @@ __global__ void s2_prepack_dma_kernel(const float* __restrict__ w, float* __rest
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int c = grp * 8 + j;
-        const float x = co < cout ? w[(((int64_t)co * cin + c) * 4 + dy) * 4 + dx] * scale : 0.0f;
-        const _Float16 h = (_Float16)x;
-        v[j] = kind == 0 ? h : (_Float16)(x - (float)h);
+        v[j] = fldr_pack_half(co < cout ? w[(((int64_t)co * cin + c) * 4 + dy) * 4 + dx] * scale : 0.0f, kind);
     }
     reinterpret_cast<s2_h8*>(dst)[i] = v;
 }
@@ -1318,7 +1295,7 @@ extern "C" int fldr_conv_s2_prepack(const float* weight, float* wpack, int cout,
     int mt, nmt;
     s2_geometry(cout, mt, nmt);
     const int64_t first = s2_first_section_floats(cout, cin), total_h8 = first / 4;
-    hipLaunchKernelGGL(s2_absmax_kernel, dim3(1), dim3(256), 0, fldr_s(stream), weight, (int64_t)cout * cin * 16, wpack);
+    hipLaunchKernelGGL(fldr_pack_absmax_kernel<S2_HDR>, dim3(1), dim3(256), 0, fldr_s(stream), weight, (int64_t)cout * cin * 16, wpack);
     hipLaunchKernelGGL(s2_prepack_kernel, dim3(fldr_cdiv(total_h8, 256)), dim3(256), 0, fldr_s(stream), weight, wpack, cout, cin, mt, nmt,
                        total_h8);
     if (s2_has_dma_section(cout, cin)) {
@@ -1332,7 +1309,7 @@ extern "C" int fldr_conv_s2_prepack(const float* weight, float* wpack, int cout,
 template <int MT, int NMT, int PT>
 static int s2_launch(S2Args& a, int N, hipStream_t s) {
     using Cfg = S2Cfg<MT, NMT>;
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv4x4s2_split_kernel<MT, NMT, PT>), Cfg::LDS_BYTES, attr_done)) return e;
     a.tiles_x = fldr_cdiv(a.Wout, S2_TW);
     const int tiles_y = fldr_cdiv(a.out_rows, S2_TH);
@@ -1356,17 +1333,24 @@ static inline int s2_wgs(int tiles_per_xcd, int cap) {
     return w < g_s2_wgs_max ? w : g_s2_wgs_max;
 }
 
+// The tile / XCD / workgroup arithmetic of the persistent launchers: the tile grid starts x_shift output columns left of the image, tiles
+// are numbered over all samples in XCD-contiguous ranges, at most `cap` workgroups per XCD walk them.
+static int s2_fill_persistent(S2Args& a, int N, int x_shift, int cap) {
+    a.x_shift = x_shift;
+    a.tiles_x = fldr_cdiv(a.Wout + a.x_shift, S2_TW);
+    a.n_tiles = a.tiles_x * fldr_cdiv(a.out_rows, S2_TH);
+    a.N = N;
+    const int64_t total = (int64_t)N * a.n_tiles;
+    if (total >= (1ll << 30)) return FLDR_E_SHAPE;
+    a.tiles_per_xcd = (int)((total + 7) / 8);
+    a.wgs_per_xcd = s2_wgs(a.tiles_per_xcd, cap);
+    return 0;
+}
+
 template <int MT, int NMT, int PT, bool V4>
 static int s2_launch_pers2(S2Args& a, hipStream_t s, int lds_bytes) {
-    static std::atomic<int> attr_bytes[64];                      // per device ordinal: the attribute is per device
-    int dev = 0;
-    if (hipError_t e = hipGetDevice(&dev); e != hipSuccess) return (int)e;
-    if (attr_bytes[dev & 63].load(std::memory_order_acquire) < lds_bytes) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv4x4s2_pers_kernel<MT, NMT, PT, V4>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
-        if (e != hipSuccess) return (int)e;
-        attr_bytes[dev & 63].store(lds_bytes, std::memory_order_release);
-    }
+    static FldrLdsLimit attr_done;
+    if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv4x4s2_pers_kernel<MT, NMT, PT, V4>), lds_bytes, attr_done)) return e;
     hipLaunchKernelGGL((conv4x4s2_pers_kernel<MT, NMT, PT, V4>), dim3(8 * a.wgs_per_xcd), dim3(256), lds_bytes, s, a);
     FLDR_LAUNCH_RET();
 }
@@ -1380,14 +1364,7 @@ static int s2_launch_pers(S2Args& a, int N, hipStream_t s, int lds_bytes) {
     // 128-byte line ([64 t - 31, 64 t + 34]) and touch 3 lines per row instead of the 4 of the unshifted span
     // [64 t - 1, 64 t + 64] (one float each into the lines left and right).  PMC at 4K, enc1: the L2 fetched 1,629 MB for
     // 920 MB of planes and the kernel ran at the fabric's ~6.4 TB/s; one extra, partly filled tile column pays for it.
-    a.x_shift = g_s2_xshift >= 0 ? g_s2_xshift : (a.Wout >= 256 ? 15 : 0);
-    a.tiles_x = fldr_cdiv(a.Wout + a.x_shift, S2_TW);
-    a.n_tiles = a.tiles_x * fldr_cdiv(a.out_rows, S2_TH);
-    a.N = N;
-    const int64_t total = (int64_t)N * a.n_tiles;
-    if (total >= (1ll << 30)) return FLDR_E_SHAPE;
-    a.tiles_per_xcd = (int)((total + 7) / 8);
-    a.wgs_per_xcd = s2_wgs(a.tiles_per_xcd, 64);
+    if (int e = s2_fill_persistent(a, N, g_s2_xshift >= 0 ? g_s2_xshift : (a.Wout >= 256 ? 15 : 0), 64)) return e;
     // 16-byte staging: the window start ix0 - 1 = 64 t - 2 x_shift - 2 is a multiple of 4 floats for odd shifts; rows and
     // planes must keep that alignment
     bool v4 = g_s2_vec4 && (a.x_shift & 1) && (a.Win & 3) == 0;
@@ -1404,13 +1381,27 @@ static int s2_set_rows(S2Args& a, int out_rows, int src_rows) {
     return 0;
 }
 
+// What both entry points below ask of a descriptor's geometry, and everything of S2Args that is copied from the descriptor and the
+// row limits (the sources, and a pair's second problem, are the callers').
+static int s2_check_geometry(const fldr_conv_desc* d) {
+    FLDR_CHECK_ARG(d->cout_store > 0 && d->cout_store <= d->cout && d->ksize == 4 && d->stride == 2);
+    if (d->Hout != (d->Hin + 2 - 4) / 2 + 1 || d->Wout != (d->Win + 2 - 4) / 2 + 1) return FLDR_E_SHAPE;
+    if (d->Hin < 2 || d->Win < 2) return FLDR_E_SHAPE;             // no output row / column ((1 + 2 - 4) / 2 truncates to 0 above: the size is floor(-1 / 2) + 1 = 0)
+    return 0;
+}
+static int s2_fill_args(S2Args& a, const fldr_conv_desc* d, int out_rows, int src_rows) {
+    a.wpack = d->wpack; a.bias = d->bias; a.out = d->out; a.out_spk = reinterpret_cast<unsigned char*>(d->out_spk);
+    a.wpack2 = nullptr; a.bias2 = nullptr; a.out2 = nullptr; a.out_spk2 = nullptr;
+    a.cin = d->cin; a.cout = d->cout; a.cout_store = d->cout_store;
+    a.Hin = d->Hin; a.Win = d->Win; a.Hout = d->Hout; a.Wout = d->Wout; a.relu = d->relu; a.tiles_x = 0;
+    return s2_set_rows(a, out_rows, src_rows);
+}
+
 // Same descriptor as fldr_conv2d (ksize 4, stride 2; no up2 sources, no residual); d->wpack from fldr_conv_s2_prepack.
 static int s2_split_run(const fldr_conv_desc* d, int out_rows, int src_rows, fldr_stream_t stream) {
     FLDR_CHECK_ARG(d && d->wpack && (d->out || d->out_spk) && d->n_src >= 1 && d->n_src <= FLDR_CONV_MAX_SRC);
     FLDR_CHECK_ARG(d->N > 0 && d->cin > 0 && d->cin <= 112 && d->cout > 0 && d->cout <= 64 && !d->residual);
-    FLDR_CHECK_ARG(d->cout_store > 0 && d->cout_store <= d->cout && d->ksize == 4 && d->stride == 2);
-    if (d->Hout != (d->Hin + 2 - 4) / 2 + 1 || d->Wout != (d->Win + 2 - 4) / 2 + 1) return FLDR_E_SHAPE;
-    if (d->Hin < 2 || d->Win < 2) return FLDR_E_SHAPE;             // no output row / column ((1 + 2 - 4) / 2 truncates to 0 above: the size is floor(-1 / 2) + 1 = 0)
+    if (int e = s2_check_geometry(d)) return e;
     S2Args a;
     int csum = 0;
     for (int s = 0; s < FLDR_CONV_MAX_SRC; ++s) {
@@ -1425,10 +1416,7 @@ static int s2_split_run(const fldr_conv_desc* d, int out_rows, int src_rows, fld
     a.src_cbegin[FLDR_CONV_MAX_SRC] = csum;
     if (csum != d->cin) return FLDR_E_SHAPE;
     a.n_src = d->n_src;
-    a.wpack = d->wpack; a.bias = d->bias; a.out = d->out; a.out_spk = reinterpret_cast<unsigned char*>(d->out_spk);
-    a.cin = d->cin; a.cout = d->cout; a.cout_store = d->cout_store;
-    a.Hin = d->Hin; a.Win = d->Win; a.Hout = d->Hout; a.Wout = d->Wout; a.relu = d->relu; a.tiles_x = 0;
-    if (int e = s2_set_rows(a, out_rows, src_rows)) return e;
+    if (int e = s2_fill_args(a, d, out_rows, src_rows)) return e;
     int mt, nmt;
     s2_geometry(d->cout, mt, nmt);
     hipStream_t s = fldr_s(stream);
@@ -1451,17 +1439,10 @@ extern "C" int fldr_conv2d_s2_split_rows(const fldr_conv_desc* d, int out_rows, 
 // Persistent kernel only: cin <= 64 and every chunk's weights in LDS; FLDR_E_SHAPE otherwise.
 template <int MT, int NMT, int PT>
 static int s2_launch_pers_spk(S2Args& a, int N, hipStream_t s, int lds_bytes, int pair = 1) {
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv4x4s2_pers_spk_kernel<MT, NMT, PT>), lds_bytes, attr_done)) return e;
-    a.x_shift = 0;                                                            // (pixels are 16-byte records: every window start is aligned)
-    a.tiles_x = fldr_cdiv(a.Wout, S2_TW);
-    a.n_tiles = a.tiles_x * fldr_cdiv(a.out_rows, S2_TH);
-    a.N = N;
-    const int64_t total = (int64_t)N * a.n_tiles;
-    if (total >= (1ll << 30)) return FLDR_E_SHAPE;
-    a.tiles_per_xcd = (int)((total + 7) / 8);
-    const int cap = (lds_bytes > 80 * 1024 ? 32 : 64) / pair;                // workgroups per XCD that fit: one or two per CU (a pair launch: shared by the two problems)
-    a.wgs_per_xcd = s2_wgs(a.tiles_per_xcd, cap);
+    // no shift (pixels are 16-byte records: every window start is aligned); workgroups per XCD that fit: one or two per CU (a pair launch: shared by the two problems)
+    if (int e = s2_fill_persistent(a, N, 0, (lds_bytes > 80 * 1024 ? 32 : 64) / pair)) return e;
     hipLaunchKernelGGL((conv4x4s2_pers_spk_kernel<MT, NMT, PT>), dim3(8 * a.wgs_per_xcd, pair), dim3(256), lds_bytes, s, a);
     FLDR_LAUNCH_RET();
 }
@@ -1473,17 +1454,9 @@ static int s2_launch_pers_spk(S2Args& a, int N, hipStream_t s, int lds_bytes, in
 static int g_s2_dma = S2_DMA_DEFAULT;
 FLDR_HOOK int fldr_debug_s2_dma(int v) { if (v == 0 || v == 1) g_s2_dma = v; return g_s2_dma; }
 static int s2_launch_dma_spk(S2Args& a, int N, hipStream_t s, int lds_bytes, int pair) {
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv4x4s2_dma_spk_kernel), lds_bytes, attr_done)) return e;
-    a.x_shift = 0;
-    a.tiles_x = fldr_cdiv(a.Wout, S2_TW);
-    a.n_tiles = a.tiles_x * fldr_cdiv(a.out_rows, S2_TH);
-    a.N = N;
-    const int64_t total = (int64_t)N * a.n_tiles;
-    if (total >= (1ll << 30)) return FLDR_E_SHAPE;
-    a.tiles_per_xcd = (int)((total + 7) / 8);
-    const int cap = 32 / pair;                                               // one workgroup per CU (a pair launch: shared by the two problems)
-    a.wgs_per_xcd = s2_wgs(a.tiles_per_xcd, cap);
+    if (int e = s2_fill_persistent(a, N, 0, 32 / pair)) return e;           // one workgroup per CU (a pair launch: shared by the two problems)
     hipLaunchKernelGGL(conv4x4s2_dma_spk_kernel, dim3(8 * a.wgs_per_xcd, pair), dim3((4 + S2D_NLOAD) * 64), lds_bytes, s, a);
     FLDR_LAUNCH_RET();
 }
@@ -1491,27 +1464,21 @@ static int s2_launch_dma_spk(S2Args& a, int N, hipStream_t s, int lds_bytes, int
 static int s2_spk_run(const fldr_conv_desc* d, const fldr_conv_desc* d2, int out_rows, int src_rows, fldr_stream_t stream) {
     FLDR_CHECK_ARG(d && d->wpack && (d->out || d->out_spk) && d->n_src == 1 && d->src[0] && !d->src_up2[0] && !d->residual);
     FLDR_CHECK_ARG(d->N > 0 && d->cin > 0 && d->cin <= 64 && (d->cin & 7) == 0 && d->src_c[0] == d->cin && d->cout > 0 && d->cout <= 64);
-    FLDR_CHECK_ARG(d->cout_store > 0 && d->cout_store <= d->cout && d->ksize == 4 && d->stride == 2);
-    if (d->Hout != (d->Hin + 2 - 4) / 2 + 1 || d->Wout != (d->Win + 2 - 4) / 2 + 1) return FLDR_E_SHAPE;
+    if (int e = s2_check_geometry(d)) return e;
     if ((int64_t)d->Hin * d->Win * 16 >= (1ll << 32)) return FLDR_E_SHAPE;
-    if (d->Hin < 2 || d->Win < 2) return FLDR_E_SHAPE;             // no output row / column, as in s2_split_run
     S2Args a;
     for (int s = 0; s < FLDR_CONV_MAX_SRC; ++s) { a.src[s] = nullptr; a.src_bstride[s] = 0; a.src_cstride[s] = 0; a.src_cbegin[s] = 0; }
     a.src[0] = d->src[0]; a.src_bstride[0] = d->src_bstride[0]; a.src_cbegin[FLDR_CONV_MAX_SRC] = d->cin; a.n_src = 1;
-    a.wpack = d->wpack; a.bias = d->bias; a.out = d->out; a.out_spk = reinterpret_cast<unsigned char*>(d->out_spk);
-    a.wpack2 = nullptr; a.bias2 = nullptr; a.out2 = nullptr; a.out_spk2 = nullptr;
     int pair = 1;
     if (d2) {                                                            // the same convolution geometry on the same source, other weights / outputs
         FLDR_CHECK_ARG(d2->wpack && (d2->out || d2->out_spk) && d2->n_src == 1 && d2->src[0] == d->src[0] && d2->src_bstride[0] == d->src_bstride[0]);
         FLDR_CHECK_ARG(d2->N == d->N && d2->cin == d->cin && d2->src_c[0] == d->cin && d2->cout == d->cout && d2->cout_store == d->cout_store && !d2->residual);
         FLDR_CHECK_ARG(d2->Hin == d->Hin && d2->Win == d->Win && d2->Hout == d->Hout && d2->Wout == d->Wout && d2->relu == d->relu && d2->ksize == 4 && d2->stride == 2);
         FLDR_CHECK_ARG(!d2->bias == !d->bias && !d2->out == !d->out && !d2->out_spk == !d->out_spk);
-        a.wpack2 = d2->wpack; a.bias2 = d2->bias; a.out2 = d2->out; a.out_spk2 = reinterpret_cast<unsigned char*>(d2->out_spk);
         pair = 2;
     }
-    a.cin = d->cin; a.cout = d->cout; a.cout_store = d->cout_store;
-    a.Hin = d->Hin; a.Win = d->Win; a.Hout = d->Hout; a.Wout = d->Wout; a.relu = d->relu; a.tiles_x = 0;
-    if (int e = s2_set_rows(a, out_rows, src_rows)) return e;
+    if (int e = s2_fill_args(a, d, out_rows, src_rows)) return e;
+    if (d2) { a.wpack2 = d2->wpack; a.bias2 = d2->bias; a.out2 = d2->out; a.out_spk2 = reinterpret_cast<unsigned char*>(d2->out_spk); }
     int mt, nmt;
     s2_geometry(d->cout, mt, nmt);
     const int n_chunks = d->cin / S2_CC;

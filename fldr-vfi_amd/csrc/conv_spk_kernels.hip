@@ -572,50 +572,6 @@ extern "C" int fldr_spk_unpack(const void* src, float* dst, int N, int C, int H,
 // weights: same body layout as conv_split_kernels.hip ([group][chunk][step][m][kind][lane][8 halves]) behind an
 // 8-float header whose second half is the zero block
 // ------------------------------------------------------------------------------------------------
-__global__ void spk_absmax_kernel(const float* __restrict__ w, int64_t n, float* __restrict__ hdr) {
-    __shared__ float red[256];
-    float m = 0.0f;
-    for (int64_t i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(w[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x < SPK_HDR) {
-        const float mx = red[0];
-        float scale = 1.0f;                                  // largest power of two with mx * scale <= 8192
-        if (mx > 0.0f) scale = exp2f(floorf(log2f(8192.0f / mx)));
-        const float v[SPK_HDR] = {1.0f / scale, scale, mx, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-        hdr[threadIdx.x] = v[threadIdx.x];
-    }
-}
-
-__global__ void spk_prepack_kernel(const float* __restrict__ w, float* __restrict__ wp, int cout, int cin, int nmt,
-                                   int n_chunks, int64_t total_h8) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= total_h8) return;
-    const float scale = wp[1];
-    const int lane = (int)(i % 64);
-    const int kind = (int)((i / 64) % 2);
-    const int m = (int)((i / 128) % nmt);
-    const int s = (int)((i / (128 * nmt)) % SPK_STEPS);
-    const int ch = (int)((i / (128 * nmt * SPK_STEPS)) % n_chunks);
-    const int gr = (int)(i / ((int64_t)128 * nmt * SPK_STEPS * n_chunks));
-    const int li = lane & 15, lg = lane >> 4;
-    const int co = gr * 16 * nmt + m * 16 + li;
-    const int tap = 2 * s + (lg >> 1);
-    h8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int c = ch * 16 + (lg & 1) * 8 + j;
-        float x = (tap < 9 && co < cout && c < cin) ? w[((int64_t)co * cin + c) * 9 + tap] * scale : 0.0f;
-        const _Float16 h = (_Float16)x;
-        v[j] = kind == 0 ? h : (_Float16)(x - (float)h);
-    }
-    reinterpret_cast<h8*>(wp + SPK_HDR)[i] = v;
-}
-
 // section R32: [group of 32 outputs][chunk][tap][hi, lo][lane = channel-group-of-the-chunk * 32 + output][8 channels]
 __global__ void spk_prepack32_kernel(const float* __restrict__ w, const float* __restrict__ hdr, float* __restrict__ dst, int cout, int cin,
                                      int n_chunks, int64_t total_h8) {
@@ -629,9 +585,7 @@ __global__ void spk_prepack32_kernel(const float* __restrict__ w, const float* _
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int c = ch * 16 + (lane >> 5) * 8 + j;
-        const float x = (co < cout && c < cin) ? w[((int64_t)co * cin + c) * 9 + tap] * scale : 0.0f;
-        const _Float16 h = (_Float16)x;
-        v[j] = kind == 0 ? h : (_Float16)(x - (float)h);
+        v[j] = fldr_pack_half((co < cout && c < cin) ? w[((int64_t)co * cin + c) * 9 + tap] * scale : 0.0f, kind);
     }
     reinterpret_cast<h8*>(dst)[i] = v;
 }
@@ -645,17 +599,11 @@ extern "C" int fldr_conv_spk_prepack(const float* weight, float* wpack, int cout
     FLDR_CHECK_ARG(weight && wpack);
     const int64_t total = fldr_conv_spk_prepack_size(cout, cin);
     if (total < 0) return (int)total;
-    int nmt, groups;
-    spk_geometry(cout, nmt, groups);
-    const int n_chunks = (cin + 15) / 16;
-    const int64_t first = spk_first_section_floats(cout, cin), total_h8 = first / 4;
-    hipLaunchKernelGGL(spk_absmax_kernel, dim3(1), dim3(256), 0, fldr_s(stream), weight, (int64_t)cout * cin * 9, wpack);
-    hipLaunchKernelGGL(spk_prepack_kernel, dim3(fldr_cdiv(total_h8, 256)), dim3(256), 0, fldr_s(stream), weight, wpack, cout, cin,
-                       nmt, n_chunks, total_h8);
+    fldr_prepack3x3_launch<SPK_HDR>(weight, wpack, cout, cin, fldr_s(stream));
     if (spk_has_r32_section(cout)) {
         const int64_t r_h8 = spk_r32_section_floats(cout, cin) / 4;
-        hipLaunchKernelGGL(spk_prepack32_kernel, dim3(fldr_cdiv(r_h8, 256)), dim3(256), 0, fldr_s(stream), weight, wpack, wpack + SPK_HDR + first,
-                           cout, cin, n_chunks, r_h8);
+        hipLaunchKernelGGL(spk_prepack32_kernel, dim3(fldr_cdiv(r_h8, 256)), dim3(256), 0, fldr_s(stream), weight, wpack,
+                           wpack + SPK_HDR + spk_first_section_floats(cout, cin), cout, cin, (cin + 15) / 16, r_h8);
     }
     FLDR_LAUNCH_RET();
 }
@@ -674,7 +622,7 @@ FLDR_HOOK int fldr_debug_spk_variant(int v) { if (v >= 0) g_spk_variant = v; ret
 template <int NMT, int TERMS, bool HAS_RES>
 static int spk_launch2(SpkArgs& a, int N, hipStream_t s) {
     using Cfg = SpkCfg<NMT>;
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv3x3_spk_kernel<NMT, TERMS, HAS_RES>), Cfg::LDS_BYTES, attr_done)) return e;
     if (int e = spk_fill_geometry(a, N, g_spk_wgs_per_xcd)) return e;
     hipLaunchKernelGGL((conv3x3_spk_kernel<NMT, TERMS, HAS_RES>), dim3(8 * a.wgs_per_xcd), dim3(512), Cfg::LDS_BYTES, s, a);
@@ -686,6 +634,25 @@ static int spk_launch(SpkArgs& a, int N, hipStream_t s) {
     return a.residual ? spk_launch2<NMT, TERMS, true>(a, N, s) : spk_launch2<NMT, TERMS, false>(a, N, s);
 }
 #endif  // FLDR_TEST_HOOKS
+
+// The group table of a descriptor's concatenated packed sources.  whole_groups: every source is a multiple of 8 channels (the ringrow
+// experiment: FLDR_E_ARG otherwise); else only the last source may end in a partial group (FLDR_E_SHAPE otherwise).
+static int spk_fill_groups(SpkArgs& a, const fldr_spk_conv_desc* d, bool whole_groups) {
+    int gsum = 0, csum = 0;
+    for (int s = 0; s < d->n_src; ++s) {
+        FLDR_CHECK_ARG(d->src[s] && d->src_c[s] > 0 && !(whole_groups && (d->src_c[s] & 7)));
+        if (d->src_up2[s] && ((d->H | d->W) & 1)) return FLDR_E_SHAPE;
+        if (s + 1 < d->n_src && (d->src_c[s] & 7)) return FLDR_E_SHAPE;
+        const int ng = (d->src_c[s] + 7) / 8;
+        if (gsum + ng > SPK_MAX_GROUPS) return FLDR_E_ARG;
+        const int64_t plane = d->src_up2[s] ? (int64_t)(d->H >> 1) * (d->W >> 1) * 16 : (int64_t)d->H * d->W * 16;
+        spk_put_groups(a, gsum, ng, d->src[s], plane, d->src_up2[s] != 0, d->src_bstride[s]);
+        gsum += ng; csum += d->src_c[s];
+    }
+    if (csum != d->cin) return FLDR_E_SHAPE;
+    spk_end_groups(a, gsum);
+    return 0;
+}
 
 // rows (0 = all): fldr_conv2d_spk_rows' limit; the ring pipeline walks the tile rows that hold output rows below it, every other path computes everything
 static int spk_conv_run(const fldr_spk_conv_desc* d, int rows, fldr_stream_t stream) {
@@ -699,22 +666,7 @@ static int spk_conv_run(const fldr_spk_conv_desc* d, int rows, fldr_stream_t str
     if ((int64_t)d->cout_store * d->H * d->W * 4 >= (1ll << 32) || fldr_spk_bytes(96, d->H, d->W) >= (1ll << 32)) return FLDR_E_SHAPE;
     SpkArgs a;
     a.res_spk = (d->precision & 2) ? 1 : 0;
-    int gsum = 0, csum = 0;
-    for (int s = 0; s < d->n_src; ++s) {
-        FLDR_CHECK_ARG(d->src[s] && d->src_c[s] > 0);
-        if (d->src_up2[s] && ((d->H | d->W) & 1)) return FLDR_E_SHAPE;
-        if (s + 1 < d->n_src && (d->src_c[s] & 7)) return FLDR_E_SHAPE;      // only the last source may have a partial group
-        const int ng = (d->src_c[s] + 7) / 8;
-        if (gsum + ng > SPK_MAX_GROUPS) return FLDR_E_ARG;
-        const int64_t plane = d->src_up2[s] ? (int64_t)(d->H >> 1) * (d->W >> 1) * 16 : (int64_t)d->H * d->W * 16;
-        for (int g = 0; g < ng; ++g) {
-            a.grp_ptr[gsum + g] = (unsigned long long)(reinterpret_cast<uintptr_t>(d->src[s]) + (uint64_t)g * 2 * plane) | (d->src_up2[s] ? 1ull : 0ull);
-            a.grp_bstride[gsum + g] = d->src_bstride[s];
-        }
-        gsum += ng; csum += d->src_c[s];
-    }
-    if (csum != d->cin) return FLDR_E_SHAPE;
-    for (int g = gsum; g < SPK_MAX_GROUPS; ++g) { a.grp_ptr[g] = 0ull; a.grp_bstride[g] = 0; }
+    if (int e = spk_fill_groups(a, d, false)) return e;
     a.n_levels = 0;
     a.wpack = d->wpack; a.bias = d->bias; a.residual = d->residual;
     a.out_f32 = d->out_f32; a.out_spk = reinterpret_cast<unsigned char*>(d->out_spk);
@@ -722,7 +674,7 @@ static int spk_conv_run(const fldr_spk_conv_desc* d, int rows, fldr_stream_t str
     a.n_chunks = (d->cin + 15) / 16; a.cout = d->cout; a.cout_store = d->cout_store;
     a.H = d->H; a.W = d->W; a.relu = d->relu;
     int nmt, groups;
-    spk_geometry(d->cout, nmt, groups);
+    fldr_conv3x3_geometry(d->cout, nmt, groups);
     a.groups = groups; a.pack_nmt = nmt;
     a.w32_off = spk_has_r32_section(d->cout) ? (SPK_HDR + spk_first_section_floats(d->cout, d->cin)) * 4 : 0;
     // Small launches (the coarse pyramid levels): fewer units than CUs, and every workgroup would stream the weights
@@ -738,14 +690,7 @@ static int spk_conv_run(const fldr_spk_conv_desc* d, int rows, fldr_stream_t str
 #ifndef FLDR_TEST_HOOKS
     return FLDR_E_ARG;                                               // (unreachable: the variant switch is a test-build hook)
 #else
-    if (d->precision & 1) {
-        if (nmt == 1) return spk_launch<1, 1>(a, d->N, s);
-        if (nmt == 2) return spk_launch<2, 1>(a, d->N, s);
-        return spk_launch<3, 1>(a, d->N, s);
-    }
-    if (nmt == 1) return spk_launch<1, 3>(a, d->N, s);
-    if (nmt == 2) return spk_launch<2, 3>(a, d->N, s);
-    return spk_launch<3, 3>(a, d->N, s);
+    return fldr_dispatch_nmt_terms(nmt, (d->precision & 1) ? 1 : 3, [&](auto NMT, auto TERMS) { return spk_launch<NMT(), TERMS()>(a, d->N, s); });
 #endif
 }
 extern "C" int fldr_conv2d_spk(const fldr_spk_conv_desc* d, fldr_stream_t stream) { return spk_conv_run(d, 0, stream); }
@@ -763,21 +708,7 @@ FLDR_HOOK int fldr_debug_conv2d_ringrow(const fldr_spk_conv_desc* d, const float
     if (fldr_spk_bytes(96, d->H, d->W) >= (1ll << 32)) return FLDR_E_SHAPE;
     SpkArgs a;
     a.res_spk = 0;
-    int gsum = 0;
-    for (int s = 0; s < d->n_src; ++s) {
-        FLDR_CHECK_ARG(d->src[s] && d->src_c[s] > 0 && !(d->src_c[s] & 7));
-        if (d->src_up2[s] && ((d->H | d->W) & 1)) return FLDR_E_SHAPE;
-        const int ng = d->src_c[s] / 8;
-        if (gsum + ng > SPK_MAX_GROUPS) return FLDR_E_ARG;
-        const int64_t plane = d->src_up2[s] ? (int64_t)(d->H >> 1) * (d->W >> 1) * 16 : (int64_t)d->H * d->W * 16;
-        for (int g = 0; g < ng; ++g) {
-            a.grp_ptr[gsum + g] = (unsigned long long)(reinterpret_cast<uintptr_t>(d->src[s]) + (uint64_t)g * 2 * plane) | (d->src_up2[s] ? 1ull : 0ull);
-            a.grp_bstride[gsum + g] = d->src_bstride[s];
-        }
-        gsum += ng;
-    }
-    if (gsum * 8 != d->cin) return FLDR_E_SHAPE;
-    for (int g = gsum; g < SPK_MAX_GROUPS; ++g) { a.grp_ptr[g] = 0ull; a.grp_bstride[g] = 0; }
+    if (int e = spk_fill_groups(a, d, true)) return e;
     a.n_levels = 0;
     a.wpack = d->wpack; a.bias = d->bias; a.residual = nullptr; a.out_f32 = nullptr;
     a.out_spk = reinterpret_cast<unsigned char*>(d->out_spk);
@@ -805,15 +736,15 @@ extern "C" int fldr_conv2d_spk_levels(const fldr_spk_conv_desc* descs, int n_lev
     FLDR_CHECK_ARG(!(d0.precision & ~3) && (!(d0.precision & 2) || d0.residual));
     SpkArgs a;
     a.res_spk = (d0.precision & 2) ? 1 : 0;
-    const int ng = (d0.cin + 7) / 8;
-    for (int g = 0; g < SPK_MAX_GROUPS; ++g) { a.grp_ptr[g] = g < ng ? (unsigned long long)reinterpret_cast<uintptr_t>(d0.src[0]) : 0ull; a.grp_bstride[g] = 0; }
+    spk_put_groups(a, 0, (d0.cin + 7) / 8, d0.src[0], 0, false, 0);               // (the levels' offsets: a.lv below)
+    spk_end_groups(a, (d0.cin + 7) / 8);
     a.wpack = d0.wpack; a.bias = d0.bias; a.residual = d0.residual;
     a.out_f32 = d0.out_f32; a.out_spk = reinterpret_cast<unsigned char*>(d0.out_spk);
     a.out_spk_bstride = 0;
     a.n_chunks = (d0.cin + 15) / 16; a.cout = d0.cout; a.cout_store = d0.cout_store;
     a.H = d0.H; a.W = d0.W; a.relu = d0.relu;
     int nmt, groups;
-    spk_geometry(d0.cout, nmt, groups);
+    fldr_conv3x3_geometry(d0.cout, nmt, groups);
     a.groups = groups; a.pack_nmt = nmt; a.w32_off = 0;
     a.n_levels = n_levels;
     int64_t units = 0;

@@ -20,7 +20,7 @@
 //     and the slab is filled by LDS-DMA (global_load_lds_dwordx4) with no registers involved;
 //   * inputs are prefetched into registers during the previous chunk's MFMAs (multi-source concat, nearest-x2 and
 //     zero padding resolved at load time), then split into hi/lo and written with two ds_write_b128.
-#include "common.h"
+#include "weight_pack.h"
 #include <hip/hip_fp16.h>
 
 #ifdef FLDR_STAMPS
@@ -51,6 +51,7 @@ typedef __attribute__((address_space(3))) void* slptr_t;
 #define SP_IN_BYTES (4 * SP_CG_STRIDE)          // hi[2 planes] + lo[2 planes]
 #define SP_STEPS 5                              // tap pairs per 16-channel chunk (9 taps + 1 zero tap)
 #define SP_HDR 4                                // floats before the packed weights: {1/scale, -, -, -}
+static_assert(SP_STEPS == FLDR_PACK3X3_STEPS, "weight_pack.h: steps per chunk of the 3x3 pack");
 
 struct SplitArgs {
     // per input channel (after concatenation) of sample 0: plane pointer, bit 0 = "stored at half resolution, read
@@ -348,64 +349,12 @@ __global__ __launch_bounds__(512, 2) void conv3x3_split_kernel(SplitArgs a) {
 
 // ------------------------------------------------------------------------------------------------
 // prepack: max|w| -> power-of-two scale -> hi/lo halves in MFMA A-operand order
-//   layout after the 4-float header: [group][chunk][step][m][kind hi|lo][lane][8 halves]
+//   layout after the 4-float header: [group][chunk][step][m][kind hi|lo][lane][8 halves] (weight_pack.h: fldr_prepack3x3_kernel)
 // ------------------------------------------------------------------------------------------------
-static inline void split_geometry(int cout, int& nmt, int& groups) {
-    if (cout <= 16)      { nmt = 1; groups = 1; }
-    else if (cout <= 32) { nmt = 2; groups = 1; }
-    else if (cout <= 48) { nmt = 3; groups = 1; }
-    else if (cout <= 64) { nmt = 2; groups = 2; }
-    else                 { nmt = 3; groups = (cout + 47) / 48; }
-}
-
-__global__ void split_absmax_kernel(const float* __restrict__ w, int64_t n, float* __restrict__ hdr) {
-    __shared__ float red[256];
-    float m = 0.0f;
-    for (int64_t i = threadIdx.x; i < n; i += 256) m = fmaxf(m, fabsf(w[i]));
-    red[threadIdx.x] = m;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + s]);
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-        const float mx = red[0];
-        // largest power of two with mx * scale <= 8192 (fp16 max 65504); all-zero weights: scale 1
-        float scale = 1.0f;
-        if (mx > 0.0f) scale = exp2f(floorf(log2f(8192.0f / mx)));
-        hdr[0] = 1.0f / scale; hdr[1] = scale; hdr[2] = mx; hdr[3] = 0.0f;
-    }
-}
-
-__global__ void split_prepack_kernel(const float* __restrict__ w, float* __restrict__ wp, int cout, int cin, int nmt,
-                                     int n_chunks, int64_t total_h8) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;          // one 8-half (16-byte) element per thread
-    if (i >= total_h8) return;
-    const float scale = wp[1];
-    const int lane = (int)(i % 64);
-    const int kind = (int)((i / 64) % 2);
-    const int m = (int)((i / 128) % nmt);
-    const int s = (int)((i / (128 * nmt)) % SP_STEPS);
-    const int ch = (int)((i / (128 * nmt * SP_STEPS)) % n_chunks);
-    const int gr = (int)(i / ((int64_t)128 * nmt * SP_STEPS * n_chunks));
-    const int li = lane & 15, lg = lane >> 4;
-    const int co = gr * 16 * nmt + m * 16 + li;
-    const int tap = 2 * s + (lg >> 1);
-    h8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int c = ch * 16 + (lg & 1) * 8 + j;
-        float x = (tap < 9 && co < cout && c < cin) ? w[((int64_t)co * cin + c) * 9 + tap] * scale : 0.0f;
-        const _Float16 h = (_Float16)x;
-        v[j] = kind == 0 ? h : (_Float16)(x - (float)h);
-    }
-    reinterpret_cast<h8*>(wp + SP_HDR)[i] = v;
-}
-
 extern "C" int64_t fldr_conv_split_prepack_size(int cout, int cin) {
     if (cout <= 0 || cin <= 0 || cout > 96 || cin > SP_MAX_CIN) return FLDR_E_ARG;
     int nmt, groups;
-    split_geometry(cout, nmt, groups);
+    fldr_conv3x3_geometry(cout, nmt, groups);
     const int n_chunks = (cin + 15) / 16;
     return SP_HDR + (int64_t)groups * n_chunks * SP_STEPS * nmt * 2 * 64 * 4;     // floats (8 halves = 4 floats)
 }
@@ -414,13 +363,7 @@ extern "C" int fldr_conv_split_prepack(const float* weight, float* wpack, int co
     FLDR_CHECK_ARG(weight && wpack);
     const int64_t total = fldr_conv_split_prepack_size(cout, cin);
     if (total < 0) return (int)total;
-    int nmt, groups;
-    split_geometry(cout, nmt, groups);
-    const int n_chunks = (cin + 15) / 16;
-    const int64_t total_h8 = (total - SP_HDR) / 4;
-    hipLaunchKernelGGL(split_absmax_kernel, dim3(1), dim3(256), 0, fldr_s(stream), weight, (int64_t)cout * cin * 9, wpack);
-    hipLaunchKernelGGL(split_prepack_kernel, dim3(fldr_cdiv(total_h8, 256)), dim3(256), 0, fldr_s(stream), weight, wpack, cout, cin,
-                       nmt, n_chunks, total_h8);
+    fldr_prepack3x3_launch<SP_HDR>(weight, wpack, cout, cin, fldr_s(stream));
     FLDR_LAUNCH_RET();
 }
 
@@ -430,7 +373,7 @@ static int split_launch(const SplitArgs& a, int N, hipStream_t s) {
     SplitArgs b = a;
     b.tiles_x = fldr_cdiv(a.W, SP_TW);
     const int tiles_y = fldr_cdiv(a.H, SP_TH);
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&conv3x3_split_kernel<NMT, TERMS>), Cfg::LDS_BYTES, attr_done)) return e;
     b.n_tiles = b.tiles_x * tiles_y;
     b.tiles_per_xcd = (b.n_tiles + 7) / 8;
@@ -464,15 +407,9 @@ extern "C" int fldr_conv2d_split(const fldr_conv_desc* d, fldr_stream_t stream) 
     a.cin = d->cin; a.cout = d->cout; a.cout_store = d->cout_store;
     a.H = d->Hin; a.W = d->Win; a.relu = d->relu; a.tiles_x = 0;
     int nmt, groups;
-    split_geometry(d->cout, nmt, groups);
+    fldr_conv3x3_geometry(d->cout, nmt, groups);
     a.groups = groups;
     hipStream_t s = fldr_s(stream);
-    if (d->precision == 1) {                           // plain fp16 inputs
-        if (nmt == 1) return split_launch<1, 1>(a, d->N, s);
-        if (nmt == 2) return split_launch<2, 1>(a, d->N, s);
-        return split_launch<3, 1>(a, d->N, s);
-    }
-    if (nmt == 1) return split_launch<1, 3>(a, d->N, s);
-    if (nmt == 2) return split_launch<2, 3>(a, d->N, s);
-    return split_launch<3, 3>(a, d->N, s);
+    return fldr_dispatch_nmt_terms(nmt, d->precision == 1 ? 1 : 3,                           // precision 1: plain fp16 inputs
+                                   [&](auto NMT, auto TERMS) { return split_launch<NMT(), TERMS()>(a, d->N, s); });
 }

@@ -245,7 +245,7 @@ FLDR_HOOK int fldr_debug_corr_chunk(int v) { if (v == 8 || v == 16) g_corr_cc = 
 template <int CC>
 static int corr_dma_launch(const float* a, const float* b, float* out, int N, int C, int H, int W, hipStream_t s) {
     constexpr int LDS = 2 * (CC * CORR_TH * (CORR_TW / 4) + CC * CORR_BH * (CORR_BW / 4)) * 16;
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&correlation_dma_kernel<CC>), LDS, attr_done)) return e;
     CorrGrid gr;
     gr.tiles_x = fldr_cdiv(W, CORR_TW);

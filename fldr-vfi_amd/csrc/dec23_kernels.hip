@@ -24,7 +24,7 @@
 // (8 + 2) x (32 + 2) pixels dec3 reads, in dec3's LDS layout (four planes of packed records), with exact zeros outside the image
 // (dec3's zero padding).  Summation order differs from conv3x3_ring_kernel's: results agree with the two-kernel path to fp32
 // accumulation rounding (tests: error vs fp64 torch, whole-model goldens).
-#include "common.h"
+#include "weight_pack.h"
 #include "row_plan.h"
 
 #define D23_TH 8
@@ -676,20 +676,10 @@ FLDR_TU_STATUS(dec23)
 // 2 (step - 9) + (lg >> 1), group 4 + (lg & 1) (enc1; tap 9: zeros); element j = input channel 8 group + j; scaled by a power of two into
 // the fp16 range, split hi + lo.
 __global__ void dec23_prepack_kernel(const float* __restrict__ w, float* __restrict__ wp) {
-    __shared__ float red[256];
     const int tid = threadIdx.x;
-    float m = 0.0f;
-    for (int i = tid; i < 16 * 48 * 9; i += 256) m = fmaxf(m, fabsf(w[i]));
-    red[tid] = m;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] = fmaxf(red[tid], red[tid + st]);
-        __syncthreads();
-    }
-    const float mx = red[0];
-    float scale = 1.0f;                                                  // largest power of two with mx * scale <= 8192 (as spk_absmax_kernel)
-    if (mx > 0.0f) scale = exp2f(floorf(log2f(8192.0f / mx)));
-    if (tid < D23_HDR) wp[tid] = tid == 0 ? 1.0f / scale : (tid == 1 ? scale : (tid == 2 ? mx : 0.0f));
+    const FldrPackScale ps = fldr_pack_absmax(w, 16 * 48 * 9);
+    const float scale = ps.scale;
+    fldr_pack_write_header(wp, D23_HDR, ps);
     d23_h8* frag = reinterpret_cast<d23_h8*>(wp + D23_HDR);
     for (int i = tid; i < D23_KSTEPS * 2 * 64; i += 256) {
         const int lane = i & 63, kind = (i >> 6) & 1, s = i >> 7;
@@ -698,9 +688,7 @@ __global__ void dec23_prepack_kernel(const float* __restrict__ w, float* __restr
         d23_h8 v;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            const float x = tap < 9 ? w[((int64_t)co * 48 + g * 8 + j) * 9 + tap] * scale : 0.0f;
-            const _Float16 hh = (_Float16)x;
-            v[j] = kind == 0 ? hh : (_Float16)(x - (float)hh);
+            v[j] = fldr_pack_half(tap < 9 ? w[((int64_t)co * 48 + g * 8 + j) * 9 + tap] * scale : 0.0f, kind);
         }
         frag[i] = v;
     }
@@ -718,11 +706,21 @@ extern "C" int fldr_dec23_prepack(const float* dec2_weight, float* wpack, fldr_s
 static int g_d23_wgs_max = 32;
 FLDR_HOOK int fldr_debug_dec23_wgs_per_xcd(int v) { if (v > 0) g_d23_wgs_max = v; return g_d23_wgs_max; }
 
-// out_u16 (with its white level) is the fourth output form; its pairs of pixels are 32-bit stores
-static int d23_launch(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
-                      const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
-                      double* out_f64, float* out_f32, void* out_u8, uint16_t* out_u16, int maxval, int H_u8, int W_u8, int N, int H, int W, int rows, fldr_stream_t stream) {
-    FLDR_CHECK_ARG(dec1_spk && enc1_spk && w2pack && bias2 && w3m && bias3 && cand && cand_bstride && cand_cstride && t && N > 0 && H > 0 && W > 0 && rows >= 0 && rows <= H);
+// What the four entry points share; out_u16 (with its white level) is the fourth output form; its pairs of pixels are 32-bit stores
+struct D23Call {
+    const void *dec1_spk, *enc1_spk;
+    const float *w2pack, *bias2, *w3m, *bias3;
+    const float* const* cand;
+    const int64_t *cand_bstride, *cand_cstride;
+    const float* t;
+    double T_param;
+    int N, H, W;
+    fldr_stream_t stream;
+};
+#define D23_CALL D23Call{dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, N, H, W, stream}      // from an entry point's parameters
+static int d23_launch(const D23Call& c, double* out_f64, float* out_f32, void* out_u8, uint16_t* out_u16, int maxval, int H_u8, int W_u8, int rows) {
+    const int N = c.N, H = c.H, W = c.W;
+    FLDR_CHECK_ARG(c.dec1_spk && c.enc1_spk && c.w2pack && c.bias2 && c.w3m && c.bias3 && c.cand && c.cand_bstride && c.cand_cstride && c.t && N > 0 && H > 0 && W > 0 && rows >= 0 && rows <= H);
     FLDR_CHECK_ARG((out_f64 != nullptr) + (out_f32 != nullptr) + (out_u8 != nullptr) + (out_u16 != nullptr) == 1);
     if (out_u16) { FLDR_CHECK_ARG(maxval >= 1 && maxval <= 65535); out_u8 = out_u16; }
     if (out_u8) {                                                        // the cropped rounded frame: pairs of pixels are stored together
@@ -733,16 +731,16 @@ static int d23_launch(const void* dec1_spk, const void* enc1_spk, const float* w
     if ((H | W) & 3) return FLDR_E_SHAPE;                                // dec1 lives at a quarter of the resolution
     if ((int64_t)H * W * 8 >= (1ll << 32)) return FLDR_E_SHAPE;          // 32-bit byte offsets inside a plane
     FLDR_CHECK_ARG(((reinterpret_cast<uintptr_t>(out_f64) & 15) | (reinterpret_cast<uintptr_t>(out_f32) & 7)) == 0);
-    FLDR_CHECK_ARG(((reinterpret_cast<uintptr_t>(dec1_spk) | reinterpret_cast<uintptr_t>(enc1_spk) | reinterpret_cast<uintptr_t>(w2pack) | reinterpret_cast<uintptr_t>(w3m)) & 15) == 0);
+    FLDR_CHECK_ARG(((reinterpret_cast<uintptr_t>(c.dec1_spk) | reinterpret_cast<uintptr_t>(c.enc1_spk) | reinterpret_cast<uintptr_t>(c.w2pack) | reinterpret_cast<uintptr_t>(c.w3m)) & 15) == 0);
     D23Args a;
-    a.dec1 = static_cast<const unsigned char*>(dec1_spk); a.enc1 = static_cast<const unsigned char*>(enc1_spk);
-    a.w2 = w2pack; a.bias2 = bias2; a.w3 = w3m; a.bias3 = bias3;
+    a.dec1 = static_cast<const unsigned char*>(c.dec1_spk); a.enc1 = static_cast<const unsigned char*>(c.enc1_spk);
+    a.w2 = c.w2pack; a.bias2 = c.bias2; a.w3 = c.w3m; a.bias3 = c.bias3;
     for (int k = 0; k < 6; ++k) {
-        FLDR_CHECK_ARG(cand[k] && (((uintptr_t)cand[k]) & 7) == 0 && (cand_bstride[k] & 1) == 0 && (cand_cstride[k] & 1) == 0);
-        if (cand_cstride[k] < 0 || cand_bstride[k] < 0 || 2 * cand_cstride[k] * 4 + (int64_t)H * W * 4 >= (1ll << 32)) return FLDR_E_SHAPE;   // 32-bit offsets inside a sample
-        a.cand[k] = cand[k]; a.cand_bstride_b[k] = cand_bstride[k] * 4; a.cand_cstride_b[k] = (uint32_t)(cand_cstride[k] * 4);
+        FLDR_CHECK_ARG(c.cand[k] && (((uintptr_t)c.cand[k]) & 7) == 0 && (c.cand_bstride[k] & 1) == 0 && (c.cand_cstride[k] & 1) == 0);
+        if (c.cand_cstride[k] < 0 || c.cand_bstride[k] < 0 || 2 * c.cand_cstride[k] * 4 + (int64_t)H * W * 4 >= (1ll << 32)) return FLDR_E_SHAPE;   // 32-bit offsets inside a sample
+        a.cand[k] = c.cand[k]; a.cand_bstride_b[k] = c.cand_bstride[k] * 4; a.cand_cstride_b[k] = (uint32_t)(c.cand_cstride[k] * 4);
     }
-    a.t = t; a.poison = fldr_status_poison_ptr(); a.T = T_param;
+    a.t = c.t; a.poison = fldr_status_poison_ptr(); a.T = c.T_param;
     if (!a.poison) return FLDR_E_STATUS;
     a.out = out_f64 ? static_cast<void*>(out_f64) : (out_f32 ? static_cast<void*>(out_f32) : out_u8);
     a.maxval = out_u16 ? maxval : 255;
@@ -756,49 +754,37 @@ static int d23_launch(const void* dec1_spk, const void* enc1_spk, const float* w
     a.per_xcd = (a.total + 7) / 8;
     a.wgs_per_xcd = a.per_xcd < 32 ? a.per_xcd : 32;                     // one workgroup per CU (159 KB of LDS)
     if (a.wgs_per_xcd > g_d23_wgs_max) a.wgs_per_xcd = g_d23_wgs_max;
-    static std::atomic<uint64_t> attr64{0}, attr32{0}, attr8{0}, attr16{0};
-    if (out_f64) {
-        if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&dec23_synth_kernel<double>), D23_LDS, attr64)) return e;
-        hipLaunchKernelGGL((dec23_synth_kernel<double>), dim3(8 * a.wgs_per_xcd), dim3(D23_THREADS), D23_LDS, fldr_s(stream), a);
-    } else if (out_f32) {
-        if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&dec23_synth_kernel<float>), D23_LDS, attr32)) return e;
-        hipLaunchKernelGGL((dec23_synth_kernel<float>), dim3(8 * a.wgs_per_xcd), dim3(D23_THREADS), D23_LDS, fldr_s(stream), a);
-    } else if (out_u16) {
-        if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&dec23_synth_kernel<uint16_t>), D23_LDS, attr16)) return e;
-        hipLaunchKernelGGL((dec23_synth_kernel<uint16_t>), dim3(8 * a.wgs_per_xcd), dim3(D23_THREADS), D23_LDS, fldr_s(stream), a);
-    } else {
-        if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&dec23_synth_kernel<uint8_t>), D23_LDS, attr8)) return e;
-        hipLaunchKernelGGL((dec23_synth_kernel<uint8_t>), dim3(8 * a.wgs_per_xcd), dim3(D23_THREADS), D23_LDS, fldr_s(stream), a);
-    }
+    // one instantiation per output form, each with its own LDS limit
+    void (*const kernels[4])(D23Args) = {dec23_synth_kernel<double>, dec23_synth_kernel<float>, dec23_synth_kernel<uint16_t>, dec23_synth_kernel<uint8_t>};
+    static FldrLdsLimit attr_done[4];
+    const int form = out_f64 ? 0 : (out_f32 ? 1 : (out_u16 ? 2 : 3));
+    if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(kernels[form]), D23_LDS, attr_done[form])) return e;
+    hipLaunchKernelGGL(kernels[form], dim3(8 * a.wgs_per_xcd), dim3(D23_THREADS), D23_LDS, fldr_s(c.stream), a);
     FLDR_LAUNCH_RET();
 }
 
 extern "C" int fldr_dec23_synth(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
                                 const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
                                 double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, fldr_stream_t stream) {
-    return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, out_f64, out_f32, out_u8, nullptr, 0,
-                      H_u8, W_u8, N, H, W, 0, stream);
+    return d23_launch(D23_CALL, out_f64, out_f32, out_u8, nullptr, 0, H_u8, W_u8, 0);
 }
 
 extern "C" int fldr_dec23_synth_rows(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
                                      const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
                                      double* out_f64, float* out_f32, uint8_t* out_u8, int H_u8, int W_u8, int N, int H, int W, int rows, fldr_stream_t stream) {
-    return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, out_f64, out_f32, out_u8, nullptr, 0,
-                      H_u8, W_u8, N, H, W, rows, stream);
+    return d23_launch(D23_CALL, out_f64, out_f32, out_u8, nullptr, 0, H_u8, W_u8, rows);
 }
 
 extern "C" int fldr_dec23_synth_u16(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
                                     const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
                                     uint16_t* out_u16, int maxval, int H_u16, int W_u16, int N, int H, int W, fldr_stream_t stream) {
     FLDR_CHECK_ARG(out_u16);
-    return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, nullptr, nullptr, nullptr, out_u16, maxval,
-                      H_u16, W_u16, N, H, W, 0, stream);
+    return d23_launch(D23_CALL, nullptr, nullptr, nullptr, out_u16, maxval, H_u16, W_u16, 0);
 }
 
 extern "C" int fldr_dec23_synth_u16_rows(const void* dec1_spk, const void* enc1_spk, const float* w2pack, const float* bias2, const float* w3m, const float* bias3,
                                          const float* const cand[6], const int64_t cand_bstride[6], const int64_t cand_cstride[6], const float* t, double T_param,
                                          uint16_t* out_u16, int maxval, int H_u16, int W_u16, int N, int H, int W, int rows, fldr_stream_t stream) {
     FLDR_CHECK_ARG(out_u16);
-    return d23_launch(dec1_spk, enc1_spk, w2pack, bias2, w3m, bias3, cand, cand_bstride, cand_cstride, t, T_param, nullptr, nullptr, nullptr, out_u16, maxval,
-                      H_u16, W_u16, N, H, W, rows, stream);
+    return d23_launch(D23_CALL, nullptr, nullptr, nullptr, out_u16, maxval, H_u16, W_u16, rows);
 }

@@ -12,7 +12,7 @@
 // 222 us without the convolution, 235 us without the candidate loads — co-limited by the vector ALUs (768 packed fp32
 // FMAs + ~670 fp64 operations per thread, ~600 of them the six fp64 exponentials of each pixel) and the 991 MB it
 // moves (18 candidate planes in, the fp64 frame out).
-#include "common.h"
+#include "weight_pack.h"
 
 #define D3_CIN 16
 #define D3_COUT 6
@@ -406,7 +406,6 @@ extern "C" int fldr_dec3_synth_spk(const void* d2_spk, const float* wm, const fl
 // of dec3_prepack_kernel, scaled by a power of two into the fp16 range and split into hi + lo.
 __global__ void dec3_prepack_spk_kernel(const float* __restrict__ w, float* __restrict__ wm) {
     __shared__ float we[D3_CIN * 4 * D3_COUT * 4];
-    __shared__ float red[256];
     const int tid = threadIdx.x;
     float m = 0.0f;
     for (int i = tid; i < D3_CIN * 4 * D3_COUT * 4; i += 256) {
@@ -421,16 +420,9 @@ __global__ void dec3_prepack_spk_kernel(const float* __restrict__ w, float* __re
         we[i] = sum;
         m = fmaxf(m, fabsf(sum));
     }
-    red[tid] = m;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-        if (tid < st) red[tid] = fmaxf(red[tid], red[tid + st]);
-        __syncthreads();
-    }
-    const float mx = red[0];
-    float scale = 1.0f;                                                  // largest power of two with mx * scale <= 8192 (as spk_absmax_kernel)
-    if (mx > 0.0f) scale = exp2f(floorf(log2f(8192.0f / mx)));
-    if (tid < D3M_HDR) wm[tid] = tid == 0 ? 1.0f / scale : (tid == 1 ? scale : (tid == 2 ? mx : 0.0f));
+    const FldrPackScale ps = fldr_pack_scale_of(m);                      // (its barrier also publishes we[])
+    const float scale = ps.scale;
+    fldr_pack_write_header(wm, D3M_HDR, ps);
     d3_h8* frag = reinterpret_cast<d3_h8*>(wm + D3M_HDR);
     for (int i = tid; i < 16 * 64; i += 256) {
         const int lane = i & 63, blk = i >> 6;
@@ -440,9 +432,7 @@ __global__ void dec3_prepack_spk_kernel(const float* __restrict__ w, float* __re
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int c = g * 8 + j;
-            const float x = co < D3_COUT ? we[((c * 4 + ph) * D3_COUT + co) * 4 + tap] * scale : 0.0f;
-            const _Float16 hh = (_Float16)x;
-            v[j] = kind == 0 ? hh : (_Float16)(x - (float)hh);
+            v[j] = fldr_pack_half(co < D3_COUT ? we[((c * 4 + ph) * D3_COUT + co) * 4 + tap] * scale : 0.0f, kind);
         }
         frag[i] = v;
     }

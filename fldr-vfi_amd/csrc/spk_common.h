@@ -2,7 +2,7 @@
 // conv_ring_kernels.hip: loader / consumer ring): argument block, LDS stage geometry, the hi/lo split and the MFMA /
 // LDS-read interleave patterns.
 #pragma once
-#include "common.h"
+#include "weight_pack.h"
 #include "row_plan.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -22,6 +22,7 @@ static_assert(SPK_TH == FLDR_PLAN_TH_CONV, "row_plan.h: 3x3 tile height");
 #define SPK_IN_BYTES (4 * SPK_PLANE)
 #define SPK_STEPS 5                             // tap pairs per 16-channel chunk (9 taps + 1 zero tap)
 #define SPK_HDR 8                               // floats before the packed weights: {1/scale, scale, max|w|, 0, 0,0,0,0}
+static_assert(SPK_STEPS == FLDR_PACK3X3_STEPS, "weight_pack.h: steps per chunk of the 3x3 pack");
 
 struct SpkArgs {
     unsigned long long grp_ptr[SPK_MAX_GROUPS];   // hi plane of input group g, sample 0; bit 0 = stored at half resolution (nearest x2 read); 0 = padding group
@@ -57,23 +58,27 @@ struct SpkArgs {
     int64_t w32_off;                              // conv3x3_ring32_kernel: byte offset of section R32 of the weight pack from wpack
 };
 
-// Output-channel geometry of the 16x16x32 kernels: 16-channel blocks per group (NMT), groups per launch.
-static inline void spk_geometry(int cout, int& nmt, int& groups) {
-    if (cout <= 16)      { nmt = 1; groups = 1; }
-    else if (cout <= 32) { nmt = 2; groups = 1; }
-    else if (cout <= 48) { nmt = 3; groups = 1; }
-    else if (cout <= 64) { nmt = 2; groups = 2; }
-    else                 { nmt = 3; groups = (cout + 47) / 48; }
-}
 // Weight pack: header, first section ([group][chunk][step][m][kind] 1-KB blocks of the 16x16x32 kernels), and — for 64 or 96 output
 // channels — section R32 ([group of 32][chunk][tap][kind] 1-KB blocks of conv3x3_ring32_kernel).  Sizes in floats.
 static inline int64_t spk_first_section_floats(int cout, int cin) {
     int nmt, groups;
-    spk_geometry(cout, nmt, groups);
+    fldr_conv3x3_geometry(cout, nmt, groups);
     return (int64_t)groups * ((cin + 15) / 16) * SPK_STEPS * nmt * 2 * 64 * 4;
 }
 static inline bool spk_has_r32_section(int cout) { return cout == 64 || cout == 96; }
 static inline int64_t spk_r32_section_floats(int cout, int cin) { return spk_has_r32_section(cout) ? (int64_t)(cout / 32) * ((cin + 15) / 16) * 18 * 256 : 0; }
+
+// Group table: entries [g0, g0 + ng) for one packed source at `base` whose 8-channel half planes are `plane` bytes (0: every group
+// at `base` — the multi-level form, whose kernel adds the level's offsets), tagged when it is stored at half resolution; then the tail.
+static inline void spk_put_groups(SpkArgs& a, int g0, int ng, const void* base, int64_t plane, bool up2, int64_t bstride) {
+    for (int g = 0; g < ng; ++g) {
+        a.grp_ptr[g0 + g] = (unsigned long long)(reinterpret_cast<uintptr_t>(base) + (uint64_t)g * 2 * plane) | (up2 ? 1ull : 0ull);
+        a.grp_bstride[g0 + g] = bstride;
+    }
+}
+static inline void spk_end_groups(SpkArgs& a, int gsum) {
+    for (int g = gsum; g < SPK_MAX_GROUPS; ++g) { a.grp_ptr[g] = 0ull; a.grp_bstride[g] = 0; }
+}
 
 template <int NMT>
 struct SpkCfg {

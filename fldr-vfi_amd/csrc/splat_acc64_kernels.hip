@@ -555,7 +555,7 @@ static int sa_launch2(SaArgs& a, int nprob, hipStream_t s) {
     constexpr int CA = MODE >= 1 ? CB + 1 : CB;
     constexpr int LDS = CA * TW * TH * 8 + SA_Q * 4 + 16 * 4 + 16 * 4 + 2 * 4 + SA_SBQ * 2;
     static_assert(LDS <= 160 * 1024, "tile does not fit the LDS");
-    static std::atomic<uint64_t> attr_done{0};
+    static FldrLdsLimit attr_done;
     if (int e = fldr_set_max_lds(reinterpret_cast<const void*>(&splat_acc64_kernel<MODE, CB, TW, TH, K, U, QUAD>), LDS, attr_done)) return e;
     a.tiles_x = fldr_cdiv(a.W, TW);
     a.st_y = fldr_cdiv(a.rows, K * TH);

@@ -390,3 +390,37 @@ def test_stride2_kernel_variants_at_tile_edges_vs_float64(hip, dev, spec, hooks)
         L.fldr_debug_s2_vec4(1)
         L.fldr_debug_s2_dma(1)
     _clean(hip)
+
+
+# ---- weight prepacks: the bytes of the recorded parent; the LDS limit across layer widths ------------------------------------------------
+def _same_digests(got, prefix_is_ringrow):
+    import prepack_cases as PC
+    want = {k: v for k, v in PC.DIGESTS.items() if k.startswith("ringrow") == prefix_is_ringrow}
+    assert set(got) == set(want)
+    wrong = sorted(k for k in got if got[k] != want[k])
+    assert not wrong, "packed bytes differ from the recorded ones: %s" % ", ".join(wrong)
+
+
+def test_prepack_bytes_are_the_recorded_ones(hip, dev):
+    """sha256 of every weight pack (header included) of fresh seeded weights — split, spk (with its R32 section), stride 2 (with and
+    without its DMA section), dec23, both dec3 forms; plain, all-zero and spiked weights — against the digests tests/prepack_cases.py
+    records from commit 80b93a2's product library, the last before the prepack kernels were merged."""
+    import prepack_cases as PC
+    _same_digests(PC.product_digests(hip, dev), False)
+
+
+def test_ringrow_prepack_bytes_are_the_recorded_ones(hip, dev, hooks):
+    """The same for the ringrow weight section, through its hook of the test build (digests: commit 80b93a2's test build)."""
+    import prepack_cases as PC
+    _same_digests(PC.ringrow_digests(hip, hooks, dev), True)
+
+
+def test_lds_limit_follows_ascending_cin(dev, clean_launcher):
+    """tests/conv_lds_child.py in a fresh process (started through the GPU-clean launcher, as every GPU child of this suite: a timeout,
+    the exit status checked): the stride-2 kernels whose dynamic LDS grows with cin, narrow layer first, every result within the
+    float64 bound.  The widths are the widest each kernel takes; 64 inputs, which none takes from a packed source, must be refused."""
+    import os
+    import sys
+    r = clean_launcher([sys.executable, os.path.join(os.path.dirname(os.path.abspath(__file__)), "conv_lds_child.py")], env=dict(os.environ), timeout=240)
+    print(r["stdout"])
+    assert r["rc"] == 0 and "lds limit child: ok" in r["stdout"], (r["rc"], r["stderr"][-3000:])
