@@ -140,27 +140,7 @@ fldr_video_frame temporal_frame(uint8_t* base, const fldr_video_format& f, int H
     return t;
 }
 
-// A frame of the stream, on the device and in pinned memory: the pitches are the row bytes rounded up to 16, so that every plane and
-// pitch is 16-byte aligned whatever W is and the weave runs its 16-byte form (the I420 chroma rows of a 720-wide frame are 360 bytes).
-constexpr int64_t SLOT_PITCH = 16;
-
-fldr_video_frame padded(uint8_t* base, const fldr_video_format& f, int H, int W) {
-    fldr_video_frame fr;
-    memset(&fr, 0, sizeof(fr));
-    int64_t off = 0;
-    for (int p = 0; p < planes_of(f.layout); ++p) {
-        fr.plane[p] = base + off;
-        fr.pitch[p] = (row_bytes(f, p, W) + SLOT_PITCH - 1) / SLOT_PITCH * SLOT_PITCH;
-        off += fr.pitch[p] * rows_of(p, H);
-    }
-    return fr;
-}
-
-int64_t padded_bytes(const fldr_video_format& f, int H, int W) {
-    int64_t n = 0;
-    for (int p = 0; p < planes_of(f.layout); ++p) n += (row_bytes(f, p, W) + SLOT_PITCH - 1) / SLOT_PITCH * SLOT_PITCH * rows_of(p, H);
-    return n;
-}
+// A frame of the stream, on the device and in pinned memory, is padded() (../video/frame_host.h): the weave runs its 16-byte form.
 
 bool tff_rate_ok(const fldr_field_config& c) { return (unsigned)c.tff <= 1u && (c.rate == 1 || c.rate == 2); }
 

@@ -21,52 +21,7 @@ using namespace fldr_sample16;
 
 #define WK_THREADS 256
 
-template <int FORM> struct Sample {
-    static constexpr bool WORDS = FORM != FORM_BYTE;
-    static constexpr int BPS = WORDS ? 2 : 1;                         // bytes per sample
-    static constexpr int NS = 16 / BPS;                               // samples per group
-    static constexpr int MX = WORDS ? 1023 : 255;
-};
-
-template <int FORM> __device__ __forceinline__ int value_of(uint32_t raw) {
-    return FORM == FORM_BYTE ? (int)raw : FORM == FORM_P010 ? (int)(raw >> 6) : (int)(raw & 0x3ffu);
-}
-
-template <int FORM> __device__ __forceinline__ uint32_t canonical(int o) { return FORM == FORM_P010 ? (uint32_t)o << 6 : (uint32_t)o; }
-
-// sample i of a group, as it sits in memory
-template <int FORM> __device__ __forceinline__ uint32_t raw_at(const uint32_t d[4], int i) {
-    return Sample<FORM>::WORDS ? (d[i >> 1] >> (16 * (i & 1))) & 0xffffu : (d[i >> 2] >> (8 * (i & 3))) & 0xffu;
-}
-
-template <int FORM> __device__ __forceinline__ void put_at(uint32_t d[4], int i, uint32_t raw) {
-    if (Sample<FORM>::WORDS) d[i >> 1] |= raw << (16 * (i & 1));
-    else d[i >> 2] |= raw << (8 * (i & 3));
-}
-
-template <int FORM> __device__ __forceinline__ uint32_t load_raw(const uint8_t* p) {
-    return Sample<FORM>::WORDS ? (uint32_t)*reinterpret_cast<const uint16_t*>(p) : (uint32_t)*p;
-}
-
-// the nv samples at p -> four dwords (the others zero); a whole group with load16
-template <int FORM, bool VEC> __device__ __forceinline__ void load_group(const uint8_t* p, int nv, uint32_t d[4]) {
-    using S = Sample<FORM>;
-    if (nv == S::NS) { load16<S::WORDS, VEC>(p, d); return; }
-    d[0] = d[1] = d[2] = d[3] = 0u;
-#pragma unroll
-    for (int i = 0; i < S::NS; ++i) if (i < nv) put_at<FORM>(d, i, load_raw<FORM>(p + i * S::BPS));
-}
-
-template <int FORM, bool VEC> __device__ __forceinline__ void store_group(uint8_t* p, int nv, const uint32_t d[4]) {
-    using S = Sample<FORM>;
-    if (VEC && nv == S::NS) { *reinterpret_cast<uint4*>(p) = make_uint4(d[0], d[1], d[2], d[3]); return; }
-#pragma unroll
-    for (int i = 0; i < S::NS; ++i) {
-        if (i >= nv) continue;
-        if (S::WORDS) reinterpret_cast<uint16_t*>(p)[i] = (uint16_t)raw_at<FORM>(d, i);
-        else p[i] = (uint8_t)raw_at<FORM>(d, i);
-    }
-}
+// A group sample by sample — Sample, value_of, canonical, raw_at, put_at, load_raw, load_group, store_group — is ../video/sample16_device.h's.
 
 // One missing row y of one group: ra / rb are the group's samples of the own rows above and below it (mirrored at the plane's edge).
 // first: the group is the row's first; behind: the samples of the row behind the group's 16 bytes.

@@ -60,23 +60,6 @@ int enqueue_measure(int H, int W, const fldr_video_format& fmt, const fldr_video
     return pulldown_measure(c, state, s);
 }
 
-// the bytes a plane occupies: [lo, hi)
-void extent(const fldr_video_frame& f, const fldr_video_format& fmt, int p, int H, int W, uintptr_t& lo, uintptr_t& hi) {
-    lo = (uintptr_t)f.plane[p];
-    hi = lo + (uintptr_t)(f.pitch[p] * (rows_of(p, H) - 1) + row_bytes(fmt, p, W));
-}
-
-bool overlaps(const fldr_video_frame& out, const fldr_video_frame& in, const fldr_video_format& fmt, int H, int W) {
-    for (int p = 0; p < planes_of(fmt.layout); ++p)
-        for (int q = 0; q < planes_of(fmt.layout); ++q) {
-            uintptr_t a0, a1, b0, b1;
-            extent(out, fmt, p, H, W, a0, a1);
-            extent(in, fmt, q, H, W, b0, b1);
-            if (a0 < b1 && b0 < a1) return true;
-        }
-    return false;
-}
-
 int check_assemble(int H, int W, const fldr_video_format* fmt, const fldr_video_frame* cur, const fldr_video_frame* prev,
                    const fldr_video_frame* next, const fldr_video_frame* out, int anchor, int match, const void* decision, int post) {
     if (!fmt || !cur || !out || !size_ok(H, W) || (unsigned)anchor > 1u || match < -1 || match > 2 || (unsigned)post > 1u) return FLDR_RATE_E_ARG;

@@ -34,14 +34,18 @@ struct RatePlan {
     int max_out;                       // ceil(B / A): the most outputs one pair has
 };
 
-// positive terms -> the plan; FLDR_RATE_E_RATIO for a ratio outside what the converter takes
-int reduce_rate(int32_t in_num, int32_t in_den, int32_t out_num, int32_t out_den, RatePlan& p) {
-    int64_t A = (int64_t)in_num * out_den, B = (int64_t)in_den * out_num;
+// positive A / B, input frames per output -> the plan; FLDR_RATE_E_RATIO for a ratio outside what the converter takes
+int plan_of_ratio(int64_t A, int64_t B, RatePlan& p) {
     reduce_terms(A, B);
     // t = (float)r / (float)B is then exact in its operands, and t < 0.5f exactly where r * 2 < B
     if (A > (1ll << 24) || B > (1ll << 24) || (B + A - 1) / A > FLDR_RATE_MAX_OUT) return FLDR_RATE_E_RATIO;
     p.A = A; p.B = B; p.max_out = (int)((B + A - 1) / A);
     return 0;
+}
+
+// positive rate terms -> the plan
+int reduce_rate(int32_t in_num, int32_t in_den, int32_t out_num, int32_t out_den, RatePlan& p) {
+    return plan_of_ratio((int64_t)in_num * out_den, (int64_t)in_den * out_num, p);
 }
 
 // The outputs of the pair (n - 1, n), by fldr_rate.h's rule: every j from the next output on with (n - 1) B <= j A < n B;

@@ -1,7 +1,8 @@
 // The host side of a luma tile measure (fldr_repeat_measure, fldr_pulldown_measure, fldr_probe_measure), written once: which frame sizes
 // the tile reduce of tile_reduce_device.h takes, the order in which several frames are checked, the check of the state, the luma planes
 // a measure call begins with, and the wait that follows a failed enqueue.  Included by ../cadence/cadence_host.hip and
-// ../pulldown/pulldown_host.hip (through cycle_stream_host.h) and by ../probe/probe_host.hip; it includes ../video/frame_host.h only, so a
+// ../pulldown/pulldown_host.hip (through cycle_stream_host.h), by ../probe/probe_host.hip and, for check_frames, by
+// ../interlace/interlace_host.hip; it includes ../video/frame_host.h only, so a
 // library that includes it calls no fldr_* function it did not call before.  Everything is in the unnamed namespace, as there.
 #pragma once
 #include "../video/frame_host.h"

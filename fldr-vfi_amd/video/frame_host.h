@@ -1,8 +1,8 @@
 // The host side of the frame contract of include/fldr_video.h (what a valid format and a valid frame are, how large a plane is) and the
 // plumbing of a stream object (fldr_video_session, fldr_rate): a device, a stream, one device block, one pinned block, packed frames in
 // them.  Included by video_host.hip, ../chroma/chroma_host.hip, ../pack10/pack10_host.hip and ../rgb/rgb_host.hip (through
-// yuv_stream_host.h), by the shutter and light libraries' host files and, through ../rate/rate_plan.h, by the rate, pipe, cadence, field
-// and pulldown libraries': each refuses exactly the frames libfldr_video.so refuses because all compile this text (the chroma, pack10
+// yuv_stream_host.h), by the shutter and light libraries' host files and, through ../rate/rate_plan.h, by the rate, pipe, cadence, field,
+// pulldown and interlace libraries': each refuses exactly the frames libfldr_video.so refuses because all compile this text (the chroma, pack10
 // and rgb libraries with their own FrameRules, below).  Everything is in the unnamed namespace: nothing here becomes a symbol of any
 // library.
 #pragma once
@@ -93,6 +93,49 @@ template <class Format> int64_t packed_bytes(const Format& fmt, int H, int W) {
     int64_t n = 0;
     for (int p = 0; p < R::planes(fmt); ++p) n += R::row_bytes(fmt, p, W) * R::rows(fmt, p, H);
     return n;
+}
+
+// A 4:2:0 frame whose pitches are the row bytes rounded up to 16, so that every plane and pitch is 16-byte aligned whatever W is and a
+// kernel over it runs its 16-byte form (the I420 chroma rows of a 720-wide frame are 360 bytes): the frames the deinterlacing and
+// interlacing streams hold on the device and in pinned memory.
+constexpr int64_t SLOT_PITCH = 16;
+
+int64_t padded_pitch(const fldr_video_format& f, int p, int W) { return (row_bytes(f, p, W) + SLOT_PITCH - 1) / SLOT_PITCH * SLOT_PITCH; }
+
+fldr_video_frame padded(uint8_t* base, const fldr_video_format& f, int H, int W) {
+    fldr_video_frame fr;
+    memset(&fr, 0, sizeof(fr));
+    int64_t off = 0;
+    for (int p = 0; p < planes_of(f.layout); ++p) {
+        fr.plane[p] = base + off;
+        fr.pitch[p] = padded_pitch(f, p, W);
+        off += fr.pitch[p] * rows_of(p, H);
+    }
+    return fr;
+}
+
+int64_t padded_bytes(const fldr_video_format& f, int H, int W) {
+    int64_t n = 0;
+    for (int p = 0; p < planes_of(f.layout); ++p) n += padded_pitch(f, p, W) * rows_of(p, H);
+    return n;
+}
+
+// the bytes a plane of a 4:2:0 frame occupies: [lo, hi)
+void extent(const fldr_video_frame& f, const fldr_video_format& fmt, int p, int H, int W, uintptr_t& lo, uintptr_t& hi) {
+    lo = (uintptr_t)f.plane[p];
+    hi = lo + (uintptr_t)(f.pitch[p] * (rows_of(p, H) - 1) + row_bytes(fmt, p, W));
+}
+
+// any plane of `out` shares a byte with any plane of `in`
+bool overlaps(const fldr_video_frame& out, const fldr_video_frame& in, const fldr_video_format& fmt, int H, int W) {
+    for (int p = 0; p < planes_of(fmt.layout); ++p)
+        for (int q = 0; q < planes_of(fmt.layout); ++q) {
+            uintptr_t a0, a1, b0, b1;
+            extent(out, fmt, p, H, W, a0, a1);
+            extent(in, fmt, q, H, W, b0, b1);
+            if (a0 < b1 && b0 < a1) return true;
+        }
+    return false;
 }
 
 // rows of every plane from `src` (any pitches) to `dst` (any pitches), on the host

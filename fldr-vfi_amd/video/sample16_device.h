@@ -2,8 +2,9 @@
 // 16 bytes of samples as four dwords (load16), the weighted add of their values (add16), the same over the frames of a launch with four
 // frames' loads in flight (gather16), the uint32 accumulator of such a group as aligned uint4 (load_acc, store_acc), and the launch of a
 // <MODE, VEC> kernel template by the sample form of a call.  Included by ../shutter/shutter_kernels.hip and ../light/light_kernels.hip
-// (all of it) and by ../rate/luma8_device.h, and through it the rate, cadence and pipe libraries (load16 and the launch).  Where a lane's
-// 16 bytes lie, what a sample's bits mean and what is done with the sums stay with the including kernel.
+// (all of it) and by ../rate/luma8_device.h, and through it the rate, cadence and pipe libraries (load16 and the launch) and the weave
+// kernels of ../field/field_kernels.hip and ../interlace/interlace_kernels.hip (a group sample by sample: Sample, value_of, canonical,
+// raw_at, put_at, load_group, store_group).  Where a lane's 16 bytes lie and what is done with the samples stay with the including kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -28,6 +29,54 @@ template <bool WORDS, bool VEC> __device__ __forceinline__ void load16(const uin
         const uint16_t* q = reinterpret_cast<const uint16_t*>(p);
 #pragma unroll
         for (int i = 0; i < 4; ++i) d[i] = (uint32_t)q[2 * i] | ((uint32_t)q[2 * i + 1] << 16);
+    }
+}
+
+// ---- a group sample by sample: what the weave kernels of the deinterlacing and interlacing libraries share ------------------------------
+template <int FORM> struct Sample {
+    static constexpr bool WORDS = FORM != FORM_BYTE;
+    static constexpr int BPS = WORDS ? 2 : 1;                         // bytes per sample
+    static constexpr int NS = 16 / BPS;                               // samples per group
+    static constexpr int MX = WORDS ? 1023 : 255;
+};
+
+template <int FORM> __device__ __forceinline__ int value_of(uint32_t raw) {
+    return FORM == FORM_BYTE ? (int)raw : FORM == FORM_P010 ? (int)(raw >> 6) : (int)(raw & 0x3ffu);
+}
+
+template <int FORM> __device__ __forceinline__ uint32_t canonical(int o) { return FORM == FORM_P010 ? (uint32_t)o << 6 : (uint32_t)o; }
+
+// sample i of a group, as it sits in memory
+template <int FORM> __device__ __forceinline__ uint32_t raw_at(const uint32_t d[4], int i) {
+    return Sample<FORM>::WORDS ? (d[i >> 1] >> (16 * (i & 1))) & 0xffffu : (d[i >> 2] >> (8 * (i & 3))) & 0xffu;
+}
+
+template <int FORM> __device__ __forceinline__ void put_at(uint32_t d[4], int i, uint32_t raw) {
+    if (Sample<FORM>::WORDS) d[i >> 1] |= raw << (16 * (i & 1));
+    else d[i >> 2] |= raw << (8 * (i & 3));
+}
+
+template <int FORM> __device__ __forceinline__ uint32_t load_raw(const uint8_t* p) {
+    return Sample<FORM>::WORDS ? (uint32_t)*reinterpret_cast<const uint16_t*>(p) : (uint32_t)*p;
+}
+
+// the nv samples at p -> four dwords (the others zero); a whole group with load16
+template <int FORM, bool VEC> __device__ __forceinline__ void load_group(const uint8_t* p, int nv, uint32_t d[4]) {
+    using S = Sample<FORM>;
+    if (nv == S::NS) { load16<S::WORDS, VEC>(p, d); return; }
+    d[0] = d[1] = d[2] = d[3] = 0u;
+#pragma unroll
+    for (int i = 0; i < S::NS; ++i) if (i < nv) put_at<FORM>(d, i, load_raw<FORM>(p + i * S::BPS));
+}
+
+template <int FORM, bool VEC> __device__ __forceinline__ void store_group(uint8_t* p, int nv, const uint32_t d[4]) {
+    using S = Sample<FORM>;
+    if (VEC && nv == S::NS) { *reinterpret_cast<uint4*>(p) = make_uint4(d[0], d[1], d[2], d[3]); return; }
+#pragma unroll
+    for (int i = 0; i < S::NS; ++i) {
+        if (i >= nv) continue;
+        if (S::WORDS) reinterpret_cast<uint16_t*>(p)[i] = (uint16_t)raw_at<FORM>(d, i);
+        else p[i] = (uint8_t)raw_at<FORM>(d, i);
     }
 }
 
