@@ -1,14 +1,15 @@
 // libfldr_field.so, host side: validation, fldr_field_weave, fldr_field_forward (measure -> t -> fldr_video_forward on the field views ->
 // weave), the schedule and the stream (woven host frames in, progressive host frames out).  The video API's rules for formats and
-// frames, and the stream / device block / pinned block the object owns, come from ../video/frame_host.h; the rule of the cut
-// thresholds from ../rate/rate_plan.h, which includes it.  The only fldr_* functions called are those of fldr_rate.h, fldr_video.h and
-// fldr_model.h.
+// frames, and the slots, the pinned frames and the two ends of a stream call (PaddedStream), come from ../video/frame_host.h; the rule
+// of the cut thresholds from ../rate/rate_plan.h, which includes it; the fill of a plane's walk from ../video/weave_walk_host.h.  The
+// only fldr_* functions called are those of fldr_rate.h, fldr_video.h and fldr_model.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
 #include <new>
 
 #include "../rate/rate_plan.h"
+#include "../video/weave_walk_host.h"
 #include "field_internal.h"
 
 using namespace fldr_field_impl;
@@ -19,8 +20,6 @@ constexpr int64_t T_BYTES = ALIGN;                                     // the t 
 constexpr uint32_t HALF_F32 = 0x3f000000u;                             // 0.5f
 
 int max_code(const fldr_video_format& f) { return deep(f) ? 1023 : 255; }
-
-bool size_ok(int H) { return H >= 4 && (H & 3) == 0; }
 
 // still and slack with the defaults filled in; FLDR_FIELD_E_ARG out of range or with a reserved word set
 int resolve_params(const fldr_field_params* p, const fldr_video_format& f, int& still, int& slack) {
@@ -45,8 +44,6 @@ fldr_video_frame field_view(const fldr_video_frame& fr, const fldr_video_format&
     return v;
 }
 
-bool aligned16(const void* p, int64_t pitch) { return (((uintptr_t)p | (uintptr_t)pitch) & 15) == 0; }
-
 // the launch arguments of a checked call; false for a frame beyond the kernel's index arithmetic (fldr_field.h: FLDR_FIELD_E_ARG)
 bool weave_args(int H, int W, const fldr_video_format& f, const fldr_video_frame& cur, const fldr_video_frame* prev, const fldr_video_frame* next,
                 const fldr_video_frame* temporal, int parity, bool intra, const uint32_t* intra_if, int still, int slack,
@@ -57,11 +54,13 @@ bool weave_args(int H, int W, const fldr_video_format& f, const fldr_video_frame
     a.intra = intra ? 1 : 0;
     a.intra_if = intra_if;
     a.still = still; a.slack = slack;
-    int64_t own_rows[3];
+    int64_t total = 0;
     for (int p = 0; p < a.planes; ++p) {
         WeavePlane& q = a.pl[p];
+        // one work item per group and own row, and the limit is judged on the own rows too (fldr_field.h)
+        const int64_t own_rows = rows_of(p, H) / 2;
+        if (!fill_walk(q, f, p, H, W, out, own_rows, own_rows, total)) return false;
         q.cur = (const uint8_t*)cur.plane[p]; q.pitch_cur = cur.pitch[p];
-        q.out = (uint8_t*)out.plane[p]; q.pitch_out = out.pitch[p];
         bool vec = aligned16(q.cur, q.pitch_cur) && aligned16(q.out, q.pitch_out);
         if (!intra) {
             q.prev = (const uint8_t*)prev->plane[p]; q.pitch_prev = prev->pitch[p];
@@ -70,24 +69,8 @@ bool weave_args(int H, int W, const fldr_video_format& f, const fldr_video_frame
             vec = vec && aligned16(q.prev, q.pitch_prev) && aligned16(q.next, q.pitch_next) && aligned16(q.temporal, q.pitch_temporal);
         }
         q.vec = vec ? 1 : 0;
-        q.row_bytes = row_bytes(f, p, W);
-        q.rows = rows_of(p, H);
         q.comp = f.layout == FLDR_VIDEO_NV12 && p == 1 ? 2 : 1;
-        const int64_t groups = (q.row_bytes + 15) / 16;
-        if (groups > 0x7fffffffll) return false;
-        q.groups = (uint32_t)groups;
-        q.groups_magic = (uint32_t)((1ull << 32) / (uint64_t)groups) + 1u;
-        own_rows[p] = q.rows / 2;
     }
-    // one work item per group and own row; the kernel's item / groups is a multiplication, exact while item x groups < 2^32
-    int64_t total = 0;
-    for (int p = 0; p < a.planes; ++p) {
-        const int64_t items = a.pl[p].groups * own_rows[p];
-        if (items * a.pl[p].groups >= (1ll << 32)) return false;
-        a.pl[p].first = (uint32_t)total;
-        total += items;
-    }
-    if (total > 0x7fffffffll) return false;
     a.total = (uint32_t)total;
     return true;
 }
@@ -114,33 +97,25 @@ int check_weave(int H, int W, const fldr_video_format* fmt, const fldr_video_fra
 // ---- the workspace of a forward: the video forward's, the scene state, the t word, the temporal frame ------------------------------
 struct FieldWs { int64_t state, t, temporal, total; };
 
+// the temporal frame: H / 2 x W, every pitch the row bytes aligned up
+constexpr int64_t TEMPORAL_PITCH = ALIGN;
+
 int64_t plan_ws(const fldr_model* m, int H, int W, FieldWs& ws) {
     if (!size_ok(H)) return FLDR_FIELD_E_SIZE;
     if (W < 2 || !m) return FLDR_FIELD_E_ARG;
     const int64_t vb = fldr_video_workspace_bytes(m, H / 2, W, 1);
     if (vb < 0) return vb;
+    fldr_video_format largest;                                         // yuv420p10le: three planes of 16-bit words
+    memset(&largest, 0, sizeof(largest));
+    largest.layout = FLDR_VIDEO_I420; largest.depth = 10;
     ws.state = align_up(vb);
     ws.t = ws.state + FLDR_SCENE_STATE_BYTES;
     ws.temporal = ws.t + T_BYTES;
-    // the largest temporal frame: yuv420p10le, luma rows of 2 W bytes and two chroma planes with rows of 2 ceil(W / 2)
-    const int64_t cw = (W + 1) / 2;
-    ws.total = ws.temporal + align_up(2ll * W) * (H / 2) + 2 * align_up(2 * cw) * (H / 4);
+    ws.total = ws.temporal + laid_out_bytes(largest, H / 2, W, TEMPORAL_PITCH);
     return ws.total;
 }
 
-fldr_video_frame temporal_frame(uint8_t* base, const fldr_video_format& f, int H, int W) {
-    fldr_video_frame t;
-    memset(&t, 0, sizeof(t));
-    int64_t off = 0;
-    for (int p = 0; p < planes_of(f.layout); ++p) {
-        t.plane[p] = base + off;
-        t.pitch[p] = align_up(row_bytes(f, p, W));
-        off += t.pitch[p] * rows_of(p, H / 2);
-    }
-    return t;
-}
-
-// A frame of the stream, on the device and in pinned memory, is padded() (../video/frame_host.h): the weave runs its 16-byte form.
+fldr_video_frame temporal_frame(uint8_t* base, const fldr_video_format& f, int H, int W) { return laid_out(base, f, H / 2, W, TEMPORAL_PITCH); }
 
 bool tff_rate_ok(const fldr_field_config& c) { return (unsigned)c.tff <= 1u && (c.rate == 1 || c.rate == 2); }
 
@@ -267,15 +242,11 @@ struct fldr_field {
     fldr_field_config cfg;
     fldr_field_params params;
     bool has_params;
-    // device: slot 0, slot 1 (frame n lives in slot n & 1), `rate` outputs, the workspace
-    // pinned: one input frame, `rate` output frames, `rate` scene results; every frame in the form of padded()
-    StreamMem sm;
-    int64_t frame_bytes, ws_bytes;
-    uint8_t* slot[2];
+    // device, behind the slots: `rate` outputs, the workspace; pinned, behind the `rate` output frames: `rate` scene results
+    PaddedStream ps;
+    int64_t ws_bytes;
     uint8_t* out_dev;
     void* ws;
-    uint8_t* in_host;
-    uint8_t* out_host;
     fldr_scene_result* scene_host;
     int64_t n;                         // frames pushed since create / reset
     int64_t j;                         // the next output
@@ -290,9 +261,10 @@ const fldr_field_params* params_of(const fldr_field* f) { return f->has_params ?
 // output k of a call: field s.field woven into the k-th device output; INTRA without a forward when `intra`
 int enqueue_output(fldr_field* f, const fldr_field_schedule& s, bool intra, int k) {
     const fldr_field_config& c = f->cfg;
-    const hipStream_t stream = f->sm.stream;
-    const fldr_video_frame cur = padded(f->slot[s.cur & 1], c.format, c.H, c.W);
-    const fldr_video_frame out = padded(f->out_dev + k * f->frame_bytes, c.format, c.H, c.W);
+    const PaddedStream& ps = f->ps;
+    const hipStream_t stream = ps.sm.stream;
+    const fldr_video_frame cur = padded_at(ps, ps.slot[s.cur & 1]);
+    const fldr_video_frame out = padded_at(ps, f->out_dev + k * ps.frame_bytes);
     memset(&f->scene_host[k], 0, sizeof(fldr_scene_result));
     if (intra)
         return fldr_field_weave(c.H, c.W, &c.format, &cur, nullptr, nullptr, nullptr, s.parity, FLDR_FIELD_INTRA, nullptr, params_of(f), &out, stream);
@@ -301,8 +273,8 @@ int enqueue_output(fldr_field* f, const fldr_field_schedule& s, bool intra, int 
     io.H = c.H; io.W = c.W;
     io.format = c.format;
     io.cur = cur;
-    io.prev = padded(f->slot[s.prev & 1], c.format, c.H, c.W);
-    io.next = padded(f->slot[s.next & 1], c.format, c.H, c.W);
+    io.prev = padded_at(ps, ps.slot[s.prev & 1]);
+    io.next = padded_at(ps, ps.slot[s.next & 1]);
     io.parity = s.parity;
     io.scene = c.scene;
     io.scene_params = c.scene_params;
@@ -314,21 +286,13 @@ int enqueue_output(fldr_field* f, const fldr_field_schedule& s, bool intra, int 
                                stream);
 }
 
-// copy `count` outputs back, wait, hand them out; on a failure the object has been reset
+// copy `count` outputs back in one piece, wait, hand them out; on a failure the object has been reset
 int finish(fldr_field* f, int rc, int count, const fldr_field_schedule* s, const bool* intra, const fldr_video_frame* host_outs, int* n_out,
            fldr_field_report* reports) {
-    const fldr_field_config& c = f->cfg;
-    const hipStream_t stream = f->sm.stream;
-    if (!rc && count) {
-        const hipError_t e = hipMemcpyAsync(f->out_host, f->out_dev, (size_t)(count * f->frame_bytes), hipMemcpyDeviceToHost, stream);
-        if (e != hipSuccess) rc = (int)e;
-    }
-    const hipError_t e = hipStreamSynchronize(stream);
-    if (!rc && e != hipSuccess) rc = (int)e;
-    if (rc) { (void)hipGetLastError(); forget(f); return rc; }
-    for (int k = 0; k < count; ++k) {
-        copy_planes(host_outs[k], padded(f->out_host + k * f->frame_bytes, c.format, c.H, c.W), c.format, c.H, c.W);
-        if (!reports) continue;
+    const uint8_t* const from = f->out_dev;
+    rc = deliver(f->ps, rc, &from, count ? 1 : 0, count * f->ps.frame_bytes, host_outs, count);
+    if (rc) { forget(f); return rc; }
+    for (int k = 0; k < count && reports; ++k) {
         fldr_field_report& r = reports[k];
         memset(&r, 0, sizeof(r));
         r.field = s[k].field;
@@ -339,13 +303,6 @@ int finish(fldr_field* f, int rc, int count, const fldr_field_schedule* s, const
     }
     *n_out = count;
     f->j += count;
-    return 0;
-}
-
-int check_outs(const fldr_field* f, const fldr_video_frame* host_outs, int count) {
-    if (!count) return 0;
-    if (!host_outs) return FLDR_FIELD_E_ARG;
-    for (int k = 0; k < count; ++k) CK(check_frame(host_outs[k], f->cfg.format, f->cfg.W));
     return 0;
 }
 
@@ -365,8 +322,7 @@ extern "C" FLDR_FIELD_API int fldr_field_create(const fldr_model* m, const fldr_
     const int H = cfg->H, W = cfg->W, rate = cfg->rate;
     const int64_t wsb = fldr_field_workspace_bytes(m, H, W);
     if (wsb < 0) return (int)wsb;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device >= ndev) { (void)hipGetLastError(); return FLDR_FIELD_E_DEVICE; }
+    if (!device_exists(cfg->device)) return FLDR_FIELD_E_DEVICE;
     fldr_field* f = new (std::nothrow) fldr_field();
     if (!f) return FLDR_FIELD_E_DEVICE;
     f->model = m;
@@ -374,18 +330,14 @@ extern "C" FLDR_FIELD_API int fldr_field_create(const fldr_model* m, const fldr_
     f->has_params = cfg->params != nullptr;
     if (f->has_params) f->params = *cfg->params;
     f->cfg.params = nullptr;
-    f->frame_bytes = align_up(padded_bytes(cfg->format, H, W));
     f->ws_bytes = wsb;
-    const int64_t dev_total = (2 + rate) * f->frame_bytes + wsb;
-    const int64_t host_total = (1 + rate) * f->frame_bytes + align_up(rate * (int64_t)sizeof(fldr_scene_result));
-    if (!open_stream_mem(f->sm, cfg->device, dev_total, host_total)) { delete f; return FLDR_FIELD_E_DEVICE; }
-    f->slot[0] = f->sm.dev;
-    f->slot[1] = f->slot[0] + f->frame_bytes;
-    f->out_dev = f->slot[1] + f->frame_bytes;
-    f->ws = f->out_dev + rate * f->frame_bytes;
-    f->in_host = f->sm.pinned;
-    f->out_host = f->in_host + f->frame_bytes;
-    f->scene_host = (fldr_scene_result*)(f->out_host + rate * f->frame_bytes);
+    if (!open_padded_stream(f->ps, cfg->device, cfg->format, H, W, rate, wsb, rate, align_up(rate * (int64_t)sizeof(fldr_scene_result)))) {
+        delete f;
+        return FLDR_FIELD_E_DEVICE;
+    }
+    f->out_dev = f->ps.dev_rest;
+    f->ws = f->out_dev + rate * f->ps.frame_bytes;
+    f->scene_host = (fldr_scene_result*)(f->ps.out_host + rate * f->ps.frame_bytes);
     forget(f);
     *out = f;
     return 0;
@@ -408,12 +360,10 @@ extern "C" FLDR_FIELD_API int fldr_field_push(fldr_field* f, const fldr_video_fr
         if (s[count].next > f->n) break;
         intra[count] = s[count].prev < 0;
     }
-    CK(check_outs(f, host_outs, count));
-    DeviceGuard g(f->sm.device);
+    CK(check_outs(f->ps, host_outs, count, FLDR_FIELD_E_ARG));
+    DeviceGuard g(f->ps.sm.device);
     if (!g.ok) return FLDR_FIELD_E_DEVICE;
-    copy_planes(padded(f->in_host, c.format, c.H, c.W), *frame, c.format, c.H, c.W);     // the gap bytes travel too, and are never read
-    const hipError_t e = hipMemcpyAsync(f->slot[f->n & 1], f->in_host, (size_t)f->frame_bytes, hipMemcpyHostToDevice, f->sm.stream);
-    int rc = e == hipSuccess ? 0 : (int)e;
+    int rc = (int)upload_input(f->ps, f->n, *frame);
     for (int k = 0; k < count && !rc; ++k) rc = enqueue_output(f, s[k], intra[k], k);
     rc = finish(f, rc, count, s, intra, host_outs, n_out, reports);
     if (!rc) f->n += 1;
@@ -428,8 +378,8 @@ extern "C" FLDR_FIELD_API int fldr_field_flush(fldr_field* f, const fldr_video_f
     schedule_of(f->cfg, f->j, s);
     if (s.cur > f->n - 1) return 0;                                    // every field of the frames pushed has gone out
     const bool intra = true;                                           // the last field has no successor
-    CK(check_outs(f, host_outs, 1));
-    DeviceGuard g(f->sm.device);
+    CK(check_outs(f->ps, host_outs, 1, FLDR_FIELD_E_ARG));
+    DeviceGuard g(f->ps.sm.device);
     if (!g.ok) return FLDR_FIELD_E_DEVICE;
     const int rc = enqueue_output(f, s, intra, 0);
     return finish(f, rc, 1, &s, &intra, host_outs, n_out, reports);
@@ -442,5 +392,5 @@ extern "C" FLDR_FIELD_API int fldr_field_reset(fldr_field* f) {
 }
 
 extern "C" FLDR_FIELD_API void fldr_field_destroy(fldr_field* f) {
-    if (f) { close_stream_mem(f->sm); delete f; }
+    if (f) { close_stream_mem(f->ps.sm); delete f; }
 }

@@ -4,13 +4,15 @@
 #include <stdint.h>
 
 #include "../rate/luma8_device.h"
+#include "../video/weave_walk_device.h"
 #include "fldr_field.h"
 
 namespace fldr_field_impl {
 using fldr_luma8::luma_mode;          // the sample form of a format: a fldr_sample16::FORM_* number
 
-// One plane of a weave.  `comp` is the distance, in samples, between neighbouring samples of one component: 2 in the interleaved
-// NV12 chroma plane, 1 elsewhere.  A work item is one 16-byte column group of one own-parity row.
+// One plane of a weave: the sources and what ../video/weave_walk_device.h says every plane carries (a work item is one 16-byte column
+// group of one own-parity row).  `comp` is the distance, in samples, between neighbouring samples of one component: 2 in the
+// interleaved NV12 chroma plane, 1 elsewhere.
 struct WeavePlane {
     const uint8_t* cur;
     const uint8_t* prev;
@@ -19,12 +21,10 @@ struct WeavePlane {
     uint8_t* out;
     int64_t pitch_cur, pitch_prev, pitch_next, pitch_temporal, pitch_out;
     int64_t row_bytes;
-    int rows;                          // R: even
+    int rows;
     int comp;                          // 1 / 2
-    int vec;                           // every address and pitch of the plane is 16-byte aligned: 16-byte loads and stores
-    uint32_t groups;                   // ceil(row_bytes / 16)
-    uint32_t groups_magic;             // floor(2^32 / groups) + 1: item / groups = umulhi(item, magic), exact while item x groups < 2^32
-    uint32_t first;                    // the plane's first work item
+    int vec;
+    uint32_t groups, groups_magic, first;
 };
 
 struct WeaveArgs {

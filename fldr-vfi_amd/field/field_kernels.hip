@@ -21,7 +21,8 @@ using namespace fldr_sample16;
 
 #define WK_THREADS 256
 
-// A group sample by sample — Sample, value_of, canonical, raw_at, put_at, load_raw, load_group, store_group — is ../video/sample16_device.h's.
+// A group sample by sample — Sample, value_of, canonical, raw_at, put_at, load_raw, load_group, store_group — is ../video/sample16_device.h's;
+// the walk — a thread's plane, its item's row and group, the 16-byte or per-sample form — ../video/weave_walk_device.h's.
 
 // One missing row y of one group: ra / rb are the group's samples of the own rows above and below it (mirrored at the plane's edge).
 // first: the group is the row's first; behind: the samples of the row behind the group's 16 bytes.
@@ -78,13 +79,13 @@ __device__ __forceinline__ void weave_row(const WeavePlane& pl, int y, int64_t x
 template <int FORM, bool VEC, int CS>
 __device__ __forceinline__ void weave_item(const WeaveArgs& a, const WeavePlane& pl, uint32_t item, bool intra) {
     using S = Sample<FORM>;
-    const uint32_t i = pl.groups == 1u ? item : __umulhi(item, pl.groups_magic), g = item - i * pl.groups;    // no division: it would go through float
-    const int64_t xoff = 16ll * g;
-    const int64_t rest = pl.row_bytes - xoff;                          // bytes of the row from this group on: > 0
+    const fldr_weave::Item it = fldr_weave::split(pl, item);
+    const int64_t xoff = it.xoff, rest = it.rest;
     const int nv = rest >= 16 ? S::NS : (int)(rest / S::BPS);
     const int64_t behind = rest >= 16 ? (rest - 16) / S::BPS : 0;
-    const bool first = g == 0;
+    const bool first = xoff == 0;
     const int n_own = pl.rows >> 1;
+    const uint32_t i = it.row;
     const int yo = a.parity + 2 * (int)i;
     uint32_t ra[4], rb[4];
     load_group<FORM, VEC>(pl.cur + (int64_t)yo * pl.pitch_cur + xoff, nv, ra);
@@ -98,26 +99,16 @@ __device__ __forceinline__ void weave_item(const WeaveArgs& a, const WeavePlane&
 
 template <int FORM>
 __global__ __launch_bounds__(WK_THREADS) void field_weave_kernel(WeaveArgs a) {
-    const uint32_t id = blockIdx.x * WK_THREADS + threadIdx.x;
-    if (id >= a.total) return;
-    const int q = (a.planes > 2 && id >= a.pl[2].first) ? 2 : (a.planes > 1 && id >= a.pl[1].first) ? 1 : 0;
-    const WeavePlane& pl = a.pl[q];
-    const bool intra = a.intra || (a.intra_if && *a.intra_if != 0u);
-    const uint32_t item = id - pl.first;
-    if (pl.vec) {
-        if (pl.comp == 2) weave_item<FORM, true, 2>(a, pl, item, intra);
-        else weave_item<FORM, true, 1>(a, pl, item, intra);
-    } else {
-        if (pl.comp == 2) weave_item<FORM, false, 2>(a, pl, item, intra);
-        else weave_item<FORM, false, 1>(a, pl, item, intra);
-    }
+    fldr_weave::walk(a, blockIdx.x * WK_THREADS + threadIdx.x, [&](const WeavePlane& pl, uint32_t item, auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        const bool intra = a.intra || (a.intra_if && *a.intra_if != 0u);
+        if (pl.comp == 2) weave_item<FORM, VEC, 2>(a, pl, item, intra);
+        else weave_item<FORM, VEC, 1>(a, pl, item, intra);
+    });
 }
 
 int weave(const WeaveArgs& a, int form, hipStream_t stream) {
-    const unsigned blocks = (a.total + WK_THREADS - 1) / WK_THREADS;
-    if (form == FORM_BYTE) field_weave_kernel<FORM_BYTE><<<blocks, WK_THREADS, 0, stream>>>(a);
-    else if (form == FORM_P010) field_weave_kernel<FORM_P010><<<blocks, WK_THREADS, 0, stream>>>(a);
-    else field_weave_kernel<FORM_LOW10><<<blocks, WK_THREADS, 0, stream>>>(a);
+    SAMPLE16_LAUNCH_FORM(field_weave_kernel, form, (a.total + WK_THREADS - 1) / WK_THREADS, WK_THREADS, stream, (a));
     return (int)hipGetLastError();
 }
 

@@ -264,11 +264,12 @@ def make_config(H, W, fmt, tff=True, rate=2, scene=True, device=0, scene_params=
     return cfg
 
 
-class Stream(fldr_video.HostStream):
+class Stream(fldr_video.ReportStream):
     """fldr_field: woven frames (tuples of numpy planes) pushed one by one; each push returns the progressive frames that became
     computable, flush() the last field at rate 2.  last_reports: one dict per frame of the last call."""
 
-    _destroy = staticmethod(lambda h: lib().fldr_field_destroy(h))
+    _lib, _check, _Report = staticmethod(lib), staticmethod(_check), Report
+    _calls = ("fldr_field_destroy", "fldr_field_push", "fldr_field_flush", "fldr_field_reset")
 
     def __init__(self, native_model, H, W, fmt=None, tff=True, rate=2, scene=True, scene_params=None, params=None):
         fmt = fmt or Format()
@@ -280,23 +281,3 @@ class Stream(fldr_video.HostStream):
         self.max_out = lib().fldr_field_max_out(self._h)
         self._stage(fmt, H, W, self.max_out)
         self.last_reports = []
-
-    def _done(self, n, reps):
-        self.last_reports = [reps[k].as_dict() for k in range(n)]
-        return self._taken(n)
-
-    def push(self, frame):
-        fr = frame_struct(frame)
-        n = ctypes.c_int(-1)
-        reps = (Report * self.max_out)()
-        _check(lib().fldr_field_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n), reps), "fldr_field_push")
-        return self._done(n.value, reps)
-
-    def flush(self):
-        n = ctypes.c_int(-1)
-        reps = (Report * self.max_out)()
-        _check(lib().fldr_field_flush(self._h, self._out_structs(), ctypes.byref(n), reps), "fldr_field_flush")
-        return self._done(n.value, reps)
-
-    def reset(self):
-        _check(lib().fldr_field_reset(self._h), "fldr_field_reset")

@@ -182,12 +182,13 @@ def plan(k, in_rate, out_rate, tff=True):
     return s.as_dict()
 
 
-class Interlacer(fldr_video.HostStream):
+class Interlacer(fldr_video.ReportStream):
     """fldr_interlace: progressive host frames (tuples of numpy planes) pushed one by one at in_rate; each push returns the woven frames
     at out_rate (interlaced frames per second) whose second field it computed, flush() the frame the end of the stream completes.
     native_model may be None where no field is interpolated (in_rate a multiple of the field rate)."""
 
-    _destroy = staticmethod(lambda h: lib().fldr_interlace_destroy(h))
+    _lib, _check, _Report = staticmethod(lib), staticmethod(_check), Report
+    _calls = ("fldr_interlace_destroy", "fldr_interlace_push", "fldr_interlace_flush", "fldr_interlace_reset")
 
     def __init__(self, native_model, H, W, fmt=None, in_rate=24, out_rate=30, tff=True, filter=LINEAR, scene=True, scene_params=None, device=0):
         fmt = fmt or Format()
@@ -202,27 +203,6 @@ class Interlacer(fldr_video.HostStream):
         self.max_out = lib().fldr_interlace_max_out(self._h)
         self._stage(fmt, H, W, self.max_out)
         self.last_reports = []
-
-    def _done(self, n, reps):
-        self.last_reports = [reps[k].as_dict() for k in range(n)]
-        return self._taken(n)
-
-    def push(self, frame):
-        """-> the list of woven frames due (tuples of numpy planes, fresh copies); self.last_reports: their report dicts."""
-        fr = frame_struct(frame)
-        n = ctypes.c_int(-1)
-        reps = (Report * self.max_out)()
-        _check(lib().fldr_interlace_push(self._h, ctypes.byref(fr), self._out_structs(), ctypes.byref(n), reps), "fldr_interlace_push")
-        return self._done(n.value, reps)
-
-    def flush(self):
-        n = ctypes.c_int(-1)
-        reps = (Report * self.max_out)()
-        _check(lib().fldr_interlace_flush(self._h, self._out_structs(), ctypes.byref(n), reps), "fldr_interlace_flush")
-        return self._done(n.value, reps)
-
-    def reset(self):
-        _check(lib().fldr_interlace_reset(self._h), "fldr_interlace_reset")
 
     def plan(self, k):
         """The schedule of output frame k of this stream -> dict."""

@@ -390,6 +390,33 @@ class HostStream:
             pass
 
 
+class ReportStream(HostStream):
+    """What fldr_field.Stream and fldr_interlace.Interlacer share: push, flush and reset of a library whose calls fill one report per
+    returned frame (last_reports: their dicts).  A subclass names `_lib` and `_check` of its module, its `_Report` struct and, in
+    `_calls`, the library's destroy, push, flush and reset; its __init__ sets `_h` and `max_out` and stages the output frames."""
+
+    def _destroy(self, h):
+        getattr(self._lib(), self._calls[0])(h)
+
+    def _run(self, what, *head):
+        n = ctypes.c_int(-1)
+        reps = (self._Report * self.max_out)()
+        self._check(getattr(self._lib(), what)(self._h, *head, self._out_structs(), ctypes.byref(n), reps), what)
+        self.last_reports = [reps[k].as_dict() for k in range(n.value)]
+        return self._taken(n.value)
+
+    def push(self, frame):
+        """-> the list of frames due (tuples of numpy planes, fresh copies); self.last_reports: their report dicts."""
+        fr = self._yuv.frame_struct(frame)
+        return self._run(self._calls[1], ctypes.byref(fr))
+
+    def flush(self):
+        return self._run(self._calls[2])
+
+    def reset(self):
+        self._check(getattr(self._lib(), self._calls[3])(self._h), self._calls[3])
+
+
 class YuvSession(HostStream):
     """The session of the library `_yuv`: host frames (tuples of numpy planes) pushed one by one; each push after the first returns n_t
     frames."""

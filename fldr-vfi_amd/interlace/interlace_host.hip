@@ -1,9 +1,10 @@
 // libfldr_interlace.so, host side: validation, fldr_interlace_weave, fldr_interlace_forward (fldr_rate_forward or fldr_video_forward into
 // temporaries -> one weave per field), the schedule and the stream (progressive host frames in, woven host frames out).  The video API's
-// rules for formats and frames, the padded frames and the stream / device block / pinned block the object owns come from
+// rules for formats and frames, the padded frames and the slots, pinned frames and two ends of a stream call (PaddedStream) come from
 // ../video/frame_host.h; the configuration rules and the schedule of the rate converter — here run at the field rate — from
-// ../rate/rate_plan.h, which includes it; the order in which several frames are checked from ../rate/tile_measure_host.h.  The only
-// fldr_* functions called are those of fldr_rate.h, fldr_video.h and fldr_model.h.
+// ../rate/rate_plan.h, which includes it; the order in which several frames are checked from ../rate/tile_measure_host.h; the fill of
+// a plane's walk from ../video/weave_walk_host.h.  The only fldr_* functions called are those of fldr_rate.h, fldr_video.h and
+// fldr_model.h.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -11,21 +12,18 @@
 
 #include "../rate/rate_plan.h"
 #include "../rate/tile_measure_host.h"
+#include "../video/weave_walk_host.h"
 #include "interlace_internal.h"
 
 using namespace fldr_interlace_impl;
 
 namespace {
 
-bool size_ok(int H) { return H >= 4 && (H & 3) == 0; }
-
 bool filter_ok(int filter) { return (unsigned)filter <= (unsigned)FLDR_INTERLACE_COMPLEX; }
 
 bool same_format(const fldr_video_format& a, const fldr_video_format& b) {
     return a.layout == b.layout && a.matrix == b.matrix && a.range == b.range && deep(a) == deep(b);
 }
-
-bool aligned16(const void* p, int64_t pitch) { return (((uintptr_t)p | (uintptr_t)pitch) & 15) == 0; }
 
 // the launch arguments of a checked call; false for a frame beyond the kernel's index arithmetic (fldr_interlace.h)
 bool weave_args(int H, int W, const fldr_video_format& f, const fldr_video_frame* even, const fldr_video_frame* odd, const fldr_video_frame& out,
@@ -37,22 +35,13 @@ bool weave_args(int H, int W, const fldr_video_format& f, const fldr_video_frame
     int64_t total = 0;
     for (int p = 0; p < a.planes; ++p) {
         WeavePlane& q = a.pl[p];
-        q.out = (uint8_t*)out.plane[p]; q.pitch_out = out.pitch[p];
+        // one work item per group and row written; the limit is that of the whole plane, whichever sources are given (fldr_interlace.h)
+        if (!fill_walk(q, f, p, H, W, out, rows_of(p, H) / a.step, rows_of(p, H), total)) return false;
         bool vec = aligned16(q.out, q.pitch_out);
         if (even) { q.even = (const uint8_t*)even->plane[p]; q.pitch_even = even->pitch[p]; vec = vec && aligned16(q.even, q.pitch_even); }
         if (odd) { q.odd = (const uint8_t*)odd->plane[p]; q.pitch_odd = odd->pitch[p]; vec = vec && aligned16(q.odd, q.pitch_odd); }
         q.vec = vec ? 1 : 0;
-        q.row_bytes = row_bytes(f, p, W);
-        q.rows = rows_of(p, H);
-        const int64_t groups = (q.row_bytes + 15) / 16;
-        // the limit is that of the whole plane, whichever sources are given; the kernel's item / groups is exact while item x groups < 2^32
-        if (groups > 0x7fffffffll || groups * q.rows * groups >= (1ll << 32)) return false;
-        q.groups = (uint32_t)groups;
-        q.groups_magic = (uint32_t)((1ull << 32) / (uint64_t)groups) + 1u;
-        q.first = (uint32_t)total;
-        total += groups * (q.rows / a.step);
     }
-    if (total > 0x7fffffffll) return false;
     a.total = (uint32_t)total;
     return true;
 }
@@ -214,17 +203,14 @@ struct fldr_interlace {
     const fldr_model* model;
     fldr_interlace_config cfg;
     RatePlan plan;                     // of the FIELDS: field m at input position m A / B; max_out fields per pair
-    // device: slot 0, slot 1 (frame n lives in slot n & 1), a ring of n_ring woven frames (frame k in k % n_ring), t, the workspace
-    // pinned: one input frame, max_frames woven frames, t, the scene result; every frame in the form of padded()
-    StreamMem sm;
-    int64_t frame_bytes, ws_bytes;
+    // device, behind the slots: a ring of n_ring woven frames (frame k in k % n_ring), t, the workspace
+    // pinned, behind the max_frames woven frames: t, the scene result
+    PaddedStream ps;
+    int64_t ws_bytes;
     int n_ring, max_frames;
-    uint8_t* slot[2];
     uint8_t* ring;
     float* t_dev;
     void* ws;
-    uint8_t* in_host;
-    uint8_t* out_host;
     float* t_host;
     fldr_scene_result* scene_host;
     fldr_interlace_report report[RING_MAX];   // of the frames in the ring, by k % n_ring
@@ -236,10 +222,9 @@ namespace {
 
 void forget(fldr_interlace* c) { c->n = 0; c->m = 0; }
 
-fldr_video_frame ring_frame(const fldr_interlace* c, int64_t k) {
-    const fldr_rate_config& r = c->cfg.rate;
-    return padded(c->ring + (k % c->n_ring) * c->frame_bytes, r.format, r.H, r.W);
-}
+uint8_t* ring_slot(const fldr_interlace* c, int64_t k) { return c->ring + (k % c->n_ring) * c->ps.frame_bytes; }
+
+fldr_video_frame ring_frame(const fldr_interlace* c, int64_t k) { return padded_at(c->ps, ring_slot(c, k)); }
 
 // field m = (i, r) enters the report of its frame; the first field of a frame begins the report
 void note_field(fldr_interlace* c, int64_t m, int64_t i, int64_t r) {
@@ -252,42 +237,26 @@ void note_field(fldr_interlace* c, int64_t m, int64_t i, int64_t r) {
 // the weave of field m straight from the input frame `i` (in its slot) into its frame of the ring
 int enqueue_direct(fldr_interlace* c, int64_t m, int64_t i) {
     const fldr_rate_config& r = c->cfg.rate;
-    const fldr_video_frame src = padded(c->slot[i & 1], r.format, r.H, r.W);
+    const fldr_video_frame src = padded_at(c->ps, c->ps.slot[i & 1]);
     const fldr_video_frame out = ring_frame(c, m >> 1);
     const int parity = (int)(m & 1) ^ (c->cfg.tff ? 0 : 1);
-    return fldr_interlace_weave(r.H, r.W, &r.format, parity ? nullptr : &src, parity ? &src : nullptr, c->cfg.filter, &out, c->sm.stream);
+    return fldr_interlace_weave(r.H, r.W, &r.format, parity ? nullptr : &src, parity ? &src : nullptr, c->cfg.filter, &out, c->ps.sm.stream);
 }
 
-int check_outs(const fldr_interlace* c, const fldr_video_frame* host_outs, int count) {
-    if (!count) return 0;
-    if (!host_outs) return FLDR_RATE_E_ARG;
-    for (int k = 0; k < count; ++k) CK(check_frame(host_outs[k], c->cfg.rate.format, c->cfg.rate.W));
-    return 0;
-}
-
-// Download the frames k0 .. k0 + count - 1, wait, hand them out with their reports; `cut`: the fields first .. first + n_fields - 1 with
-// r != 0 came from the pair whose scene result is awaited here.  On a failure the object has been reset.
+// Download the frames k0 .. k0 + count - 1, one copy each, wait, hand them out with their reports; `cut`: the fields first .. first +
+// n_fields - 1 with r != 0 came from the pair whose scene result is awaited here.  On a failure the object has been reset.
 int finish(fldr_interlace* c, int rc, int64_t k0, int count, bool measured, int64_t first, int n_fields, const fldr_video_frame* host_outs,
            int* n_out, fldr_interlace_report* reports) {
-    const fldr_rate_config& r = c->cfg.rate;
-    const hipStream_t stream = c->sm.stream;
-    for (int q = 0; q < count && !rc; ++q) {
-        const hipError_t e = hipMemcpyAsync(c->out_host + q * c->frame_bytes, c->ring + ((k0 + q) % c->n_ring) * c->frame_bytes,
-                                            (size_t)c->frame_bytes, hipMemcpyDeviceToHost, stream);
-        if (e != hipSuccess) rc = (int)e;
-    }
-    const hipError_t e = hipStreamSynchronize(stream);
-    if (!rc && e != hipSuccess) rc = (int)e;
-    if (rc) { (void)hipGetLastError(); forget(c); return rc; }
+    const uint8_t* from[RING_MAX];
+    for (int q = 0; q < count; ++q) from[q] = ring_slot(c, k0 + q);
+    rc = deliver(c->ps, rc, from, count, c->ps.frame_bytes, host_outs, count);
+    if (rc) { forget(c); return rc; }
     if (measured && c->scene_host->cut)
         for (int64_t m = first; m < first + n_fields; ++m) {
             fldr_interlace_report& rep = c->report[(m >> 1) % c->n_ring];
             if (rep.r[m & 1]) rep.cut[m & 1] = 1;
         }
-    for (int q = 0; q < count; ++q) {
-        copy_planes(host_outs[q], padded(c->out_host + q * c->frame_bytes, r.format, r.H, r.W), r.format, r.H, r.W);
-        if (reports) reports[q] = c->report[(k0 + q) % c->n_ring];
-    }
+    for (int q = 0; q < count && reports; ++q) reports[q] = c->report[(k0 + q) % c->n_ring];
     *n_out = count;
     return 0;
 }
@@ -306,8 +275,7 @@ extern "C" FLDR_INTERLACE_API int fldr_interlace_create(const fldr_model* m, con
     const int H = cfg->rate.H, W = cfg->rate.W;
     const int64_t wsb = forwards ? fldr_interlace_workspace_bytes(m, H, W, plan.max_out) : 0;
     if (wsb < 0) return (int)wsb;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->rate.device >= ndev) { (void)hipGetLastError(); return FLDR_RATE_E_DEVICE; }
+    if (!device_exists(cfg->rate.device)) return FLDR_RATE_E_DEVICE;
     fldr_interlace* c = new (std::nothrow) fldr_interlace();
     if (!c) return FLDR_RATE_E_DEVICE;
     c->model = m;
@@ -315,20 +283,16 @@ extern "C" FLDR_INTERLACE_API int fldr_interlace_create(const fldr_model* m, con
     c->plan = plan;
     c->max_frames = (plan.max_out + 1) / 2;
     c->n_ring = plan.max_out / 2 + 2;                                 // the fields of one call touch at most max_out / 2 + 1 frames
-    c->frame_bytes = align_up(padded_bytes(cfg->rate.format, H, W));
     c->ws_bytes = wsb;
     const int64_t t_bytes = align_up(4ll * plan.max_out);
-    const int64_t dev_total = (2 + c->n_ring) * c->frame_bytes + t_bytes + wsb;
-    const int64_t host_total = (1 + c->max_frames) * c->frame_bytes + t_bytes + ALIGN;
-    if (!open_stream_mem(c->sm, cfg->rate.device, dev_total, host_total)) { delete c; return FLDR_RATE_E_DEVICE; }
-    c->slot[0] = c->sm.dev;
-    c->slot[1] = c->slot[0] + c->frame_bytes;
-    c->ring = c->slot[1] + c->frame_bytes;
-    c->t_dev = (float*)(c->ring + c->n_ring * c->frame_bytes);
+    if (!open_padded_stream(c->ps, cfg->rate.device, cfg->rate.format, H, W, c->n_ring, t_bytes + wsb, c->max_frames, t_bytes + ALIGN)) {
+        delete c;
+        return FLDR_RATE_E_DEVICE;
+    }
+    c->ring = c->ps.dev_rest;
+    c->t_dev = (float*)(c->ring + c->n_ring * c->ps.frame_bytes);
     c->ws = forwards ? (uint8_t*)c->t_dev + t_bytes : nullptr;
-    c->in_host = c->sm.pinned;
-    c->out_host = c->in_host + c->frame_bytes;
-    c->t_host = (float*)(c->out_host + c->max_frames * c->frame_bytes);
+    c->t_host = (float*)(c->ps.out_host + c->max_frames * c->ps.frame_bytes);
     c->scene_host = (fldr_scene_result*)((uint8_t*)c->t_host + t_bytes);
     forget(c);
     *out = c;
@@ -351,13 +315,12 @@ extern "C" FLDR_INTERLACE_API int fldr_interlace_push(fldr_interlace* c, const f
     const int count = c->n >= 1 ? pair_outputs(c->plan, c->n, c->m, r_of, n_t) : 0;
     const int64_t k0 = c->m >> 1;                                      // the first frame this call can complete
     const int done = (int)(((c->m + count) >> 1) - k0);
-    CK(check_outs(c, host_outs, done));
-    DeviceGuard g(c->sm.device);
+    CK(check_outs(c->ps, host_outs, done, FLDR_RATE_E_ARG));
+    DeviceGuard g(c->ps.sm.device);
     if (!g.ok) return FLDR_RATE_E_DEVICE;
-    const hipStream_t stream = c->sm.stream;
-    copy_planes(padded(c->in_host, fmt, H, W), *frame, fmt, H, W);      // the gap bytes travel too, and are never read
-    hipError_t e = hipMemcpyAsync(c->slot[c->n & 1], c->in_host, (size_t)c->frame_bytes, hipMemcpyHostToDevice, stream);
-    int rc = e == hipSuccess ? 0 : (int)e;
+    const hipStream_t stream = c->ps.sm.stream;
+    hipError_t e;
+    int rc = (int)upload_input(c->ps, c->n, *frame);
     for (int k = 0; k < count; ++k) note_field(c, c->m + k, c->n - 1, r_of[k]);
     const bool measured = n_t && r.scene == 1;
     if (!rc && n_t) {
@@ -375,8 +338,8 @@ extern "C" FLDR_INTERLACE_API int fldr_interlace_push(fldr_interlace* c, const f
         memset(&io, 0, sizeof(io));
         io.pair.H = H; io.pair.W = W;
         io.pair.in_format = io.pair.out_format = fmt;
-        io.pair.in[0] = padded(c->slot[(c->n - 1) & 1], fmt, H, W);
-        io.pair.in[1] = padded(c->slot[c->n & 1], fmt, H, W);
+        io.pair.in[0] = padded_at(c->ps, c->ps.slot[(c->n - 1) & 1]);
+        io.pair.in[1] = padded_at(c->ps, c->ps.slot[c->n & 1]);
         io.pair.n_t = n_t; io.pair.t = c->t_dev; io.pair.out = outs;
         io.parity = parity;
         io.filter = c->cfg.filter;
@@ -404,8 +367,8 @@ extern "C" FLDR_INTERLACE_API int fldr_interlace_flush(fldr_interlace* c, const 
     const bool due = flush_due(c->plan, c->n, c->m);                   // field m lands exactly on the last frame
     const bool held = ((c->m + (due ? 1 : 0)) & 1) != 0;               // a frame is then left with its first field only
     if (!due && !held) return 0;
-    CK(check_outs(c, host_outs, 1));
-    DeviceGuard g(c->sm.device);
+    CK(check_outs(c->ps, host_outs, 1, FLDR_RATE_E_ARG));
+    DeviceGuard g(c->ps.sm.device);
     if (!g.ok) return FLDR_RATE_E_DEVICE;
     int rc = 0;
     int64_t m = c->m;
@@ -428,5 +391,5 @@ extern "C" FLDR_INTERLACE_API int fldr_interlace_reset(fldr_interlace* c) {
 }
 
 extern "C" FLDR_INTERLACE_API void fldr_interlace_destroy(fldr_interlace* c) {
-    if (c) { close_stream_mem(c->sm); delete c; }
+    if (c) { close_stream_mem(c->ps.sm); delete c; }
 }

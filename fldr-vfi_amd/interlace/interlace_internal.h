@@ -4,23 +4,23 @@
 #include <stdint.h>
 
 #include "../rate/luma8_device.h"
+#include "../video/weave_walk_device.h"
 #include "fldr_interlace.h"
 
 namespace fldr_interlace_impl {
 using fldr_luma8::luma_mode;          // the sample form of a format: a fldr_sample16::FORM_* number
 
-// One plane of a weave.  A work item is one 16-byte column group of one output row.
+// One plane of a weave: the sources and what ../video/weave_walk_device.h says every plane carries (a work item is one 16-byte column
+// group of one output row).
 struct WeavePlane {
     const uint8_t* even;               // the source of the rows y % 2 == 0; null: those rows are not written
     const uint8_t* odd;                // of the rows y % 2 == 1
     uint8_t* out;
     int64_t pitch_even, pitch_odd, pitch_out;
     int64_t row_bytes;
-    int rows;                          // R: even
-    int vec;                           // every address and pitch of the plane is 16-byte aligned: 16-byte loads and stores
-    uint32_t groups;                   // ceil(row_bytes / 16)
-    uint32_t groups_magic;             // floor(2^32 / groups) + 1: item / groups = umulhi(item, magic), exact while item x groups < 2^32
-    uint32_t first;                    // the plane's first work item
+    int rows;
+    int vec;
+    uint32_t groups, groups_magic, first;
 };
 
 struct WeaveArgs {

@@ -6,8 +6,8 @@
 // column group (16 samples at depth 8, 8 at depth 10) of one output row y: the lane loads that group of the 1, 3 or 5 rows y - 2 ..
 // y + 2 (clamped to the plane) of the row's source, filters and stores.  The rows of an item overlap those of the items two rows up and
 // down in the same source; the L2 serves them, so from HBM every source row wanted is read once.  All loads of an item are issued
-// before the first is used.  Consecutive lanes take consecutive groups of a row: a wave reads 1 KiB runs.  The item is split into (row,
-// group) by a multiply-high, not by a division, which would go through float.
+// before the first is used.  Consecutive lanes take consecutive groups of a row: a wave reads 1 KiB runs.  The walk — a thread's plane,
+// its item's row and group, the 16-byte or per-sample form — is ../video/weave_walk_device.h's.
 // The 16-byte loads and stores need every address and pitch of the plane 16-byte aligned (WeavePlane::vec, decided per plane); the same
 // arithmetic runs on per-sample loads and stores otherwise, and a row's last, partial group goes sample by sample in either form.
 // Under FLDR_INTERLACE_NONE the dwords are stored as they were loaded (P010: the low six bits included).
@@ -62,40 +62,24 @@ __device__ __forceinline__ void weave_group(const WeavePlane& pl, int y, int64_t
     }
 }
 
-template <int FORM, int FILTER, bool VEC>
-__device__ __forceinline__ void weave_item(const WeaveArgs& a, const WeavePlane& pl, uint32_t item) {
-    using S = Sample<FORM>;
-    const uint32_t i = pl.groups == 1u ? item : __umulhi(item, pl.groups_magic), g = item - i * pl.groups;
-    const int64_t xoff = 16ll * g;
-    const int64_t rest = pl.row_bytes - xoff;                          // bytes of the row from this group on: > 0
-    const int y = a.start + a.step * (int)i;                           // < pl.rows
-    // a whole group knows its sample count at compile time: its loads carry no test and go out together
-    if (rest >= 16) weave_group<FORM, FILTER, VEC>(pl, y, xoff, S::NS);
-    else weave_group<FORM, FILTER, VEC>(pl, y, xoff, (int)(rest / S::BPS));
-}
-
 template <int FORM, int FILTER>
 __global__ __launch_bounds__(IK_THREADS) void interlace_weave_kernel(WeaveArgs a) {
-    const uint32_t id = blockIdx.x * IK_THREADS + threadIdx.x;
-    if (id >= a.total) return;
-    const int q = (a.planes > 2 && id >= a.pl[2].first) ? 2 : (a.planes > 1 && id >= a.pl[1].first) ? 1 : 0;
-    const WeavePlane& pl = a.pl[q];
-    const uint32_t item = id - pl.first;
-    if (pl.vec) weave_item<FORM, FILTER, true>(a, pl, item);
-    else weave_item<FORM, FILTER, false>(a, pl, item);
-}
-
-template <int FORM> static void launch(const WeaveArgs& a, int filter, unsigned blocks, hipStream_t stream) {
-    if (filter == FLDR_INTERLACE_NONE) interlace_weave_kernel<FORM, FLDR_INTERLACE_NONE><<<blocks, IK_THREADS, 0, stream>>>(a);
-    else if (filter == FLDR_INTERLACE_LINEAR) interlace_weave_kernel<FORM, FLDR_INTERLACE_LINEAR><<<blocks, IK_THREADS, 0, stream>>>(a);
-    else interlace_weave_kernel<FORM, FLDR_INTERLACE_COMPLEX><<<blocks, IK_THREADS, 0, stream>>>(a);
+    const int start = a.start, step = a.step;                          // here: read inside the lambda they came late, behind a wait of their own
+    fldr_weave::walk(a, blockIdx.x * IK_THREADS + threadIdx.x, [=](const WeavePlane& pl, uint32_t item, auto vec) {
+        constexpr bool VEC = decltype(vec)::value;
+        const fldr_weave::Item it = fldr_weave::split(pl, item);
+        const int y = start + step * (int)it.row;                      // < pl.rows
+        // a whole group knows its sample count at compile time: its loads carry no test and go out together
+        if (it.rest >= 16) weave_group<FORM, FILTER, VEC>(pl, y, it.xoff, Sample<FORM>::NS);
+        else weave_group<FORM, FILTER, VEC>(pl, y, it.xoff, (int)(it.rest / Sample<FORM>::BPS));
+    });
 }
 
 int weave(const WeaveArgs& a, int form, int filter, hipStream_t stream) {
     const unsigned blocks = (a.total + IK_THREADS - 1) / IK_THREADS;
-    if (form == FORM_BYTE) launch<FORM_BYTE>(a, filter, blocks, stream);
-    else if (form == FORM_P010) launch<FORM_P010>(a, filter, blocks, stream);
-    else launch<FORM_LOW10>(a, filter, blocks, stream);
+    if (filter == FLDR_INTERLACE_NONE) SAMPLE16_LAUNCH_FORM(interlace_weave_kernel, form, blocks, IK_THREADS, stream, (a), FLDR_INTERLACE_NONE);
+    else if (filter == FLDR_INTERLACE_LINEAR) SAMPLE16_LAUNCH_FORM(interlace_weave_kernel, form, blocks, IK_THREADS, stream, (a), FLDR_INTERLACE_LINEAR);
+    else SAMPLE16_LAUNCH_FORM(interlace_weave_kernel, form, blocks, IK_THREADS, stream, (a), FLDR_INTERLACE_COMPLEX);
     return (int)hipGetLastError();
 }
 

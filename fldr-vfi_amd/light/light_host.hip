@@ -207,8 +207,7 @@ extern "C" FLDR_LIGHT_API int fldr_light_curve_create(int transfer, int depth, c
     memcpy(both.data(), c->lin, sizeof(uint32_t) * n);
     both[n] = 0;
     for (int i = 1; i < n; ++i) both[n + i] = c->lin[i - 1] + c->lin[i];
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) { (void)hipGetLastError(); delete c; return FLDR_LIGHT_E_DEVICE; }
+    if (!device_exists(device)) { delete c; return FLDR_LIGHT_E_DEVICE; }
     DeviceGuard guard(device);
     if (!guard.ok || hipMalloc((void**)&c->dev, both.size() * sizeof(uint32_t)) != hipSuccess) { (void)hipGetLastError(); delete c; return FLDR_LIGHT_E_DEVICE; }
     const hipError_t e = hipMemcpy(c->dev, both.data(), both.size() * sizeof(uint32_t), hipMemcpyHostToDevice);

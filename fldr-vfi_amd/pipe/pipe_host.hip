@@ -168,8 +168,7 @@ extern "C" FLDR_PIPE_API int fldr_pipe_create(const fldr_model* m, const fldr_pi
     const int H = cfg->H, W = cfg->W, D = pcfg->depth;
     const int64_t wsb = fldr_rate_workspace_bytes(m, H, W, max_out);
     if (wsb < 0) return (int)wsb;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device >= ndev) { (void)hipGetLastError(); return FLDR_PIPE_E_DEVICE; }
+    if (!device_exists(cfg->device)) return FLDR_PIPE_E_DEVICE;
     fldr_pipe* p = new (std::nothrow) fldr_pipe();
     if (!p) return FLDR_PIPE_E_DEVICE;
     p->model = m;

@@ -149,8 +149,7 @@ extern "C" FLDR_RATE_API int fldr_rate_create(const fldr_model* m, const fldr_ra
     const int H = cfg->H, W = cfg->W;
     const int64_t wsb = fldr_rate_workspace_bytes(m, H, W, max_out);
     if (wsb < 0) return (int)wsb;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device >= ndev) { (void)hipGetLastError(); return FLDR_RATE_E_DEVICE; }
+    if (!device_exists(cfg->device)) return FLDR_RATE_E_DEVICE;
     fldr_rate* s = new (std::nothrow) fldr_rate();
     if (!s) return FLDR_RATE_E_DEVICE;
     s->model = m;

@@ -2,8 +2,9 @@
 // the tile reduce of tile_reduce_device.h takes, the order in which several frames are checked, the check of the state, the luma planes
 // a measure call begins with, and the wait that follows a failed enqueue.  Included by ../cadence/cadence_host.hip and
 // ../pulldown/pulldown_host.hip (through cycle_stream_host.h), by ../probe/probe_host.hip and, for check_frames, by
-// ../interlace/interlace_host.hip; it includes ../video/frame_host.h only, so a
-// library that includes it calls no fldr_* function it did not call before.  Everything is in the unnamed namespace, as there.
+// ../interlace/interlace_host.hip (../field/field_host.hip checks its frames one by one and does not include it); it includes
+// ../video/frame_host.h only, so a library that includes it calls no fldr_* function it did not call before.  Everything is in the
+// unnamed namespace, as there.
 #pragma once
 #include "../video/frame_host.h"
 

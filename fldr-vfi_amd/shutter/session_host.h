@@ -186,8 +186,7 @@ int session_open(Session* s, const fldr_model* m, const fldr_shutter_config* cfg
     const int n_sub = cfg->sub - 1;
     const int64_t wsb = fldr_video_workspace_bytes(m, H, W, n_sub > 0 ? n_sub : 1);
     if (wsb < 0) return (int)wsb;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device >= ndev) { (void)hipGetLastError(); return op.e_device; }
+    if (!device_exists(cfg->device)) return op.e_device;
     s->model = m;
     s->cfg = *cfg;
     s->op = op;

@@ -4,7 +4,7 @@
 // <MODE, VEC> kernel template by the sample form of a call.  Included by ../shutter/shutter_kernels.hip and ../light/light_kernels.hip
 // (all of it) and by ../rate/luma8_device.h, and through it the rate, cadence and pipe libraries (load16 and the launch) and the weave
 // kernels of ../field/field_kernels.hip and ../interlace/interlace_kernels.hip (a group sample by sample: Sample, value_of, canonical,
-// raw_at, put_at, load_group, store_group).  Where a lane's 16 bytes lie and what is done with the samples stay with the including kernel.
+// raw_at, put_at, load_group, store_group, and the launch of a <FORM, ...> kernel template).  Where a lane's 16 bytes lie and what is done with the samples stay with the including kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -137,3 +137,9 @@ template <int SPC> __device__ __forceinline__ void store_acc(uint32_t* ap, const
         if ((mode) == fldr_sample16::FORM_BYTE) SAMPLE16_LAUNCH_VEC(KERNEL, fldr_sample16::FORM_BYTE, vec, grid, threads, stream, __VA_ARGS__); \
         else if ((mode) == fldr_sample16::FORM_P010) SAMPLE16_LAUNCH_VEC(KERNEL, fldr_sample16::FORM_P010, vec, grid, threads, stream, __VA_ARGS__); \
         else SAMPLE16_LAUNCH_VEC(KERNEL, fldr_sample16::FORM_LOW10, vec, grid, threads, stream, __VA_ARGS__); } while (0)
+// KERNEL<FORM, ...><<<grid, threads, 0, stream>>> ARGS for the form of a call: ARGS the kernel's arguments in their parentheses, ... the
+// template arguments after the form, if there are any
+#define SAMPLE16_LAUNCH_FORM(KERNEL, form, grid, threads, stream, ARGS, ...) do { \
+        if ((form) == fldr_sample16::FORM_BYTE) KERNEL<fldr_sample16::FORM_BYTE, ##__VA_ARGS__><<<grid, threads, 0, stream>>> ARGS; \
+        else if ((form) == fldr_sample16::FORM_P010) KERNEL<fldr_sample16::FORM_P010, ##__VA_ARGS__><<<grid, threads, 0, stream>>> ARGS; \
+        else KERNEL<fldr_sample16::FORM_LOW10, ##__VA_ARGS__><<<grid, threads, 0, stream>>> ARGS; } while (0)

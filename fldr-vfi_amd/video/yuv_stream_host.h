@@ -118,8 +118,7 @@ template <class L, class S> int session_create(const fldr_model* m, const typena
     const int H = cfg->H, W = cfg->W, n_t = cfg->n_t;
     const int64_t wsb = workspace_bytes<L>(m, H, W, n_t);
     if (wsb < 0) return (int)wsb;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || cfg->device >= ndev) { (void)hipGetLastError(); return L::E_DEVICE; }
+    if (!device_exists(cfg->device)) return L::E_DEVICE;
     S* s = new (std::nothrow) S();
     if (!s) return L::E_DEVICE;
     s->model = m;

@@ -35,14 +35,17 @@ def _fmt(layout, depth=8):
     return fldr_video.Format(layout, "bt709", "limited", depth)
 
 
-def _to_dev(planes, dev, pad=0, fill=0, offsets=(0, 0, 0)):
+def _to_dev(planes, dev, pad=0, fill=0, offsets=(0, 0, 0), pitch16=False):
     """Device copies of host planes (uint8 or uint16); pad / offsets in BYTES: each plane a view into a byte buffer whose rows are `pad`
-    bytes longer (gap bytes = fill), plane p starting offsets[p] bytes into its (256-byte aligned) buffer."""
+    bytes longer (gap bytes = fill), plane p starting offsets[p] bytes into its (256-byte aligned) buffer.  pitch16: every pitch is then
+    rounded up to a multiple of 16."""
     out = []
     for q, p in enumerate(planes):
         r, c = p.shape
         b = p.dtype.itemsize
         pitch = c * b + pad
+        if pitch16:
+            pitch = (pitch + 15) // 16 * 16
         off = offsets[q]
         buf = torch.full((r * pitch + off + pitch + 256,), fill, dtype=torch.uint8, device=dev)
         view = buf[off:off + r * pitch].view(r, pitch)[:, :c * b]
@@ -61,9 +64,9 @@ def _rows_with_gaps(p):
     return b.as_strided((b.shape[0], b.stride(0)), b.stride())
 
 
-def _blank_out(layout, depth, H, W, dev, pad, offsets):
+def _blank_out(layout, depth, H, W, dev, pad, offsets, pitch16=False):
     dt = np.uint16 if depth == 10 else np.uint8
-    return _to_dev([np.zeros(s, dt) for s in FF.plane_shapes(layout, H, W)], dev, pad=pad, fill=FILL, offsets=offsets)
+    return _to_dev([np.zeros(s, dt) for s in FF.plane_shapes(layout, H, W)], dev, pad=pad, fill=FILL, offsets=offsets, pitch16=pitch16)
 
 
 def _check_out(out, want):
@@ -86,12 +89,12 @@ def _untouched(out):
 
 
 def _weave_and_check(dev, layout, depth, cur, prev, nxt, temporal, parity, mode, still=None, slack=None, pad=0, offsets=(0, 0, 0), intra_if=None,
-                     want_mode=None):
+                     want_mode=None, pitch16=False):
     import fldr_field as K
     H, W = cur[0].shape
-    d = lambda fr, k: None if fr is None else _to_dev(fr, dev, pad=pad + 16 * k if pad else 0, fill=0x11 * (k + 1), offsets=offsets)
+    d = lambda fr, k: None if fr is None else _to_dev(fr, dev, pad=pad + 16 * k if pad else 0, fill=0x11 * (k + 1), offsets=offsets, pitch16=pitch16)
     frames = [d(cur, 0), d(prev, 1), d(nxt, 2), d(temporal, 3)]
-    out = _blank_out(layout, depth, H, W, dev, pad, offsets)
+    out = _blank_out(layout, depth, H, W, dev, pad, offsets, pitch16)
     params = None if still is None and slack is None else (F.defaults(depth)[0] if still is None else still, F.defaults(depth)[1] if slack is None else slack)
     K.weave(frames[0], frames[1], frames[2], frames[3], _fmt(layout, depth), parity, mode, intra_if, params, out)
     torch.cuda.synchronize()
@@ -135,6 +138,23 @@ def test_weave_with_pitches_and_offset_planes(dev, H, W, pad, misaligned, layout
     for parity in (0, 1):
         for mode in (F.INTRA, F.MOTION):
             _weave_and_check(dev, layout, depth, cur, prev, nxt, temporal, parity, mode, still=3, slack=9, pad=pad, offsets=tuple(offsets))
+
+
+@pytest.mark.parametrize("access", ["aligned", "offset"])
+@pytest.mark.parametrize("layout,depth", FF.FORMATS)
+@pytest.mark.parametrize("H,W", [(4, 70001), (2052, 3)])
+def test_weave_of_long_rows_and_of_many_rows(dev, H, W, layout, depth, access):
+    """The split of a work item into row and group, as the interlacing library's test of the same name walks it.  (4, 70001): thousands
+    of groups in a row, the last one partial, so the multiply-high does the dividing; (2052, 3): one group per row, the path without
+    the multiply, and more than a thousand own rows.  Every plane aligned and every pitch a multiple of 16 (the 16-byte form) or every
+    plane one sample into its buffer (the per-sample form); every byte against the oracle, the bytes between a row's end and its pitch
+    untouched."""
+    b = 2 if depth == 10 else 1
+    cur, prev, nxt, temporal = _noise_set(H + W + depth, layout, depth, H, W)
+    for parity in (0, 1):
+        for mode in (F.MOTION, F.INTRA):
+            _weave_and_check(dev, layout, depth, cur, prev, nxt, temporal, parity, mode, pad=16, offsets=(0, 0, 0) if access == "aligned" else (b, b, b),
+                             pitch16=True)
 
 
 @pytest.mark.parametrize("layout,depth", FF.FORMATS)
