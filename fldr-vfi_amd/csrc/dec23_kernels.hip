@@ -391,19 +391,31 @@ __global__ __launch_bounds__(D23_THREADS) void dec23_synth_kernel(D23Args a) {
             // out = sum_k wo_k cand_k / sum_k wo_k with wo_k = w_k softmax_k (fLDRnet.py:517-524): the softmax's own normalisation cancels
             // in that quotient, so the weights stay unnormalised (w_k exp(s_k - max)) — one fp64 division and six products per pixel less
             // than the literal order; the quotient differs from it by rounding only (~1e-16 relative)
-            // Instruction diet of the same quotient (every step changes the literal order's result by rounding only, ~1e-16 relative, against
-            // a 3e-6 bound): the maximum is taken on the fp32 logits (x -> x / T is monotone), logit / T - max is one fma, and the blend below
-            // is an fma chain.
+            // Instruction diet of the same quotient (every step changes the literal order's result by rounding only, ~1e-16 relative): the
+            // maximum is taken on the fp32 logits (x -> x / T is monotone), logit / T - max is one fma, and the blend below is an fma chain.
             // Round 6: the softmax weights themselves are fp32 — exp2((logit - max) * (log2 e / T)) on the transcendental unit, converted once —
             // and everything they enter (the t weights, the normalisation, the blend, the quotient) stays fp64 as in the reference.  The
             // logits are fp32 accumulations of split-fp16 products (error ~1e-6 of their magnitude): a weight computed from them is
             // uncertain by ~1e-6 relative whatever the exp's precision, and the fp32 form is within 1e-7 (dominant weights) .. 1e-6 (weights
-            // below 1e-5 of the sum) of the fp64 one — a frame difference of ~1e-7, against the 3e-6 bound of the kernel's test and the
-            // reference's own fp32 convolutions in front of this tail.  It takes 12 x 18 double-precision instructions per lane out of the
-            // ~430 that paced the consumer waves (D23_EXP_F32=0: the 16-instruction fp64 exp above).
+            // below 1e-5 of the sum) of the fp64 one — a frame difference of ~1e-7 (derived per pixel in tests/synth_float_ref.py: three
+            // fp32 roundings of the argument and the unit's own error on each weight, times the spread of the candidates; held by
+            // tests/test_gpu_synth_ops.py), against the reference's own fp32 convolutions in front of this tail.  It takes 12 x 18
+            // double-precision instructions per lane out of the ~430 that paced the consumer waves (D23_EXP_F32=0: the 16-instruction fp64
+            // exp above).
             double wo[2][6], inv_div[2];
 #if D23_EXP_F32
             const float sc2 = (float)(inv_T * 1.4426950408889634074);
+            // t == 0 or t == 1 (uniform per sample): three of the t weights are exactly 0.  The maximum below must then be taken over the
+            // other three: if it were a logit of a zero-weight candidate more than ~126 T / log2 e above every live one, exp2 would flush
+            // all three live weights to 0 and the quotient would be 0 / 0 (the fp64 exp of final_kernels.hip has 745 T of room; this one
+            // 126 T).  The zero-weight logits become -inf: they lose every maximum and exp2(-inf) = 0.  For 0 < t < 1 nothing changes.
+            if (t == 0.0f || t == 1.0f) {
+                const int dead = t == 0.0f ? 1 : 0;
+#pragma unroll
+                for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+                    for (int kc = 0; kc < 6; ++kc) acc3[rb][kc] = (kc & 1) == dead ? -__builtin_inff() : acc3[rb][kc];
+            }
 #endif
 #pragma unroll
             for (int rb = 0; rb < 2; ++rb) {
