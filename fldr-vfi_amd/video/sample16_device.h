@@ -4,7 +4,8 @@
 // <MODE, VEC> kernel template by the sample form of a call.  Included by ../shutter/shutter_kernels.hip and ../light/light_kernels.hip
 // (all of it) and by ../rate/luma8_device.h, and through it the rate, cadence and pipe libraries (load16 and the launch) and the weave
 // kernels of ../field/field_kernels.hip and ../interlace/interlace_kernels.hip (a group sample by sample: Sample, value_of, canonical,
-// raw_at, put_at, load_group, store_group, and the launch of a <FORM, ...> kernel template).  Where a lane's 16 bytes lie and what is done with the samples stay with the including kernel.
+// raw_at, put_at, load_group, store_group, and the launch of a <FORM, ...> kernel template) and the resize kernel of
+// ../scale/scale_kernels.hip (Sample, value_of, canonical, load_raw, store_group).  Where a lane's 16 bytes lie and what is done with the samples stay with the including kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
